@@ -12,7 +12,20 @@ wall time, summed over GPUs (weak scaling: every rank owns its own batch; no col
 data path — only barrier + a max-reduction of the elapsed time for reporting).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config c2|c3|c4|c5|c2copy]
+    python bench.py ... --full                # + kernel timings, roofline, probes, CPU baseline, oracle check
+    python bench.py ... --dump-outputs DIR    # + the last timed step's outputs as DIR/<name>.npy
     python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
+
+A plain run does what the headline figure needs and nothing else: it builds the batches, ramps the
+clocks, runs the W warm-up and the K timed steps and prints the line (metric, value, ms_per_step, the
+workload and the per-rank times).  `--full` adds everything else the benchmark measures or checks,
+each in passes of its own after the timed region: the per-kernel HIP-event timings and the roofline,
+the one-batch re-emit figure, the stream-read / segment / 2-B-store floor probes, C2copy's unfused TX
+path, the CPU baseline (`--cpu-seconds`) and the oracle's bit-exact check of the device's bytes.
+
+`--dump-outputs DIR` writes what a caller of the timed path holds after the last timed step (the
+emitted TX records and verify's status bytes; see dump_outputs) right after the timed region.  The
+inputs are generated from fixed seeds, so two runs with the same arguments dump the same arrays.
 
 `--gpus N` without a torch.distributed.run environment starts the N rank processes itself (one per
 GPU, before anything in this process touches a GPU); under torch.distributed.run the world size
@@ -56,8 +69,15 @@ def parse_args(argv=None):
     ap.add_argument("--ramp-ms", type=float, default=300.0,
                     help="untimed steps for at least this long before the W warm-up steps, so that the "
                          "GPU's clocks have ramped up (0: none; profiles/r03_steps/)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run everything else the benchmark measures or checks: "
+                         "per-kernel timings and roofline, the one-batch re-emit, the floor probes, C2copy's "
+                         "unfused path, the CPU baseline and the oracle check (off: the headline figure only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed step (a seeded sample of the emitted TX records "
+                         "and verify's status bytes) as DIR/<name>.npy, float32 / float64, at most 64 MB")
     ap.add_argument("--cpu-seconds", type=float, default=20.0,
-                    help="CPU-baseline budget, split between 1 thread and all threads (0: skip)")
+                    help="--full: CPU-baseline budget, split between 1 thread and all threads (0: skip)")
     ap.add_argument("--shape", type=int, default=-1, help="force a launch shape (tuning)")
     ap.add_argument("--variant", type=int, default=-1, help="force a kernel variant (tuning)")
     ap.add_argument("--emit-variant", type=int, default=-1, help="force a kernel variant for emit only (tuning)")
@@ -71,7 +91,7 @@ def parse_args(argv=None):
     ap.add_argument("--batches", type=int, default=4,
                     help="TX / RX batch pairs the steps take in turn (1: re-emit one batch; C5 always 1: its one "
                          "201-GB buffer is emitted and verified in place)")
-    ap.add_argument("--probe", action="store_true", help="(kept for old scripts: the probes always run)")
+    ap.add_argument("--probe", action="store_true", help="(kept for old scripts: the probes run with --full)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launch + rendezvous + reporting only, on CPU (gloo), no checksum work")
     return ap.parse_args(argv)
@@ -181,7 +201,11 @@ class Workload:
         eng.synth(self.tx, self.batch, self.profile, seed)
         if cfg == "c2copy":
             # payloads live in a socket-buffer-like source, back to back; headers are in the records
-            self.src = torch.randint(0, 256, (self.n * src_stride + 16,), dtype=torch.uint8, device=dev)
+            # (seeded: the same payloads in every run, so that --dump-outputs of two runs can be compared)
+            gen = torch.Generator(device=dev)
+            gen.manual_seed(seed & (2**63 - 1))
+            self.src = torch.randint(0, 256, (self.n * src_stride + 16,), dtype=torch.uint8, device=dev,
+                                     generator=gen)
             cp = E.make_copies(np.arange(self.n, dtype=np.uint64) * src_stride, 28, 1472)
             self.copy = torch.from_numpy(cp.view(np.uint8).copy()).to(dev)
             self.read_bytes = self.n * (28 + 1472)   # headers from the record, payload from the source
@@ -580,6 +604,69 @@ def load_traffic(cfg: str, kernel: str):
 
 
 # ---------------------------------------------------------------------------------------------
+# --dump-outputs
+# ---------------------------------------------------------------------------------------------
+
+DUMP_TX_BYTES = 8_000_000      # sampled TX bytes (float32: 32 MB)
+DUMP_STATUS_RECORDS = 1 << 22  # status bytes (float32: <= 16.8 MB)
+DUMP_SEED = 0x0D0C5EED
+
+
+def dump_sample(n: int, max_len: int) -> np.ndarray:
+    """The records whose TX bytes --dump-outputs writes: as many as fit DUMP_TX_BYTES at `max_len`
+    bytes each; a quarter from the head of the batch, a quarter from its tail (the first and the last
+    blocks of every launch shape), the rest drawn over the whole batch from a fixed seed.  Ascending,
+    without repeats; a function of (n, max_len) alone."""
+    m = max(1, min(n, DUMP_TX_BYTES // max(1, max_len)))
+    if m >= n:
+        return np.arange(n, dtype=np.int64)
+    q = m // 4
+    rng = np.random.default_rng(DUMP_SEED)
+    mid = rng.integers(0, n, m - 2 * q, dtype=np.int64)
+    return np.unique(np.concatenate([np.arange(q, dtype=np.int64), mid, np.arange(n - q, n, dtype=np.int64)]))
+
+
+def dump_outputs(dirpath: str, E, wl, j: int, rank: int, world: int) -> dict:
+    """Write what a caller of the timed path holds after the last timed step, which emitted TX batch
+    `j` in place and verified RX batch `j` into wl.status:
+
+      tx_records.npy   float64  the sampled record numbers (dump_sample)
+      tx_bytes.npy     float32  those records' bytes in wl.txs[j] after emit (C2copy: after the fused
+                                copy + emit), record after record, one value per byte
+      status.npy       float32  verify's status byte of every record, or of every k-th record
+                                (records 0, k, 2k, ...) when the batch has more than DUMP_STATUS_RECORDS
+
+    At world > 1 rank r writes <name>.rank<r>.npy.  Returns the summary put on the result line."""
+    import torch
+
+    os.makedirs(dirpath, exist_ok=True)
+    suffix = "" if world == 1 else f".rank{rank}"
+    tx = wl.txs[j]
+    if wl.batch.desc is None:
+        rec = dump_sample(wl.n, int(wl.batch.length))
+        o, ln = rec * int(wl.batch.stride), np.full(rec.size, int(wl.batch.length), dtype=np.int64)
+    else:
+        d = wl.batch.desc.cpu().numpy().view(E.DESC_DTYPE)
+        rec = dump_sample(wl.n, int(d["len"].max()))
+        o, ln = d["offset"][rec].astype(np.int64), d["len"][rec].astype(np.int64)
+    starts = np.cumsum(ln) - ln
+    idx = np.repeat(o - starts, ln) + np.arange(int(ln.sum()), dtype=np.int64)  # byte offsets, record after record
+    tx_bytes = tx[torch.from_numpy(idx).to(tx.device)].cpu().numpy().astype(np.float32)
+    k = -(-wl.n // DUMP_STATUS_RECORDS)
+    status = wl.status[::k].cpu().numpy().astype(np.float32)
+    files = {"tx_records": rec.astype(np.float64), "tx_bytes": tx_bytes, "status": status}
+    total = 0
+    for name, a in files.items():
+        np.save(os.path.join(dirpath, f"{name}{suffix}.npy"), a)
+        total += a.nbytes
+    return {"dir": dirpath, "files": {f"{name}{suffix}.npy": [str(a.dtype), int(a.size)] for name, a in files.items()},
+            "bytes": total, "tx_batch": j, "status_every": k,
+            "what": f"after the last timed step: the bytes of {rec.size} sampled records of TX batch {j} "
+                    f"(head, tail and a fixed-seed draw over all {wl.n}) and verify's status of "
+                    + ("every record" if k == 1 else f"every {k}-th record")}
+
+
+# ---------------------------------------------------------------------------------------------
 # One rank
 # ---------------------------------------------------------------------------------------------
 
@@ -627,9 +714,40 @@ def run_dry(args, world, rank, local):
         dist.destroy_process_group()
 
 
+def headline(args, wl, world, elapsed, R, ramp_steps, ramp_ms, backend) -> dict:
+    """The result line of a plain run (rank 0): the value over the timed region and what describes
+    the run.  --full adds its figures to the same dict."""
+    return {
+        "metric": METRIC,
+        "value": round(S.aggregate_rate(2 * wl.span_bytes, world, args.steps, elapsed), 2),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic: device-generated packets (splitmix64 payload, seeded), HBM-resident",
+        "full": bool(args.full),
+        "config": {"workload": wl.workload, "records_per_gpu": wl.n, "parallelism": f"shard x{world} (no collective)",
+                   "checksummed_bytes_per_step_per_gpu": 2 * wl.span_bytes,
+                   "process_group": backend},
+        "ramp": {"steps": ramp_steps, "ms": round(ramp_ms, 1),
+                 "what": "untimed steps before the W warm-up steps until the GPU clocks have ramped "
+                         "(steady state: profiles/r03_steps/)"},
+        "batches": {"pairs": R, "what": f"step i emits TX batch i mod {R} and verifies RX batch i mod {R}" if R > 1 else
+                    "one batch (C5: emit and verify in place over one 201-GB buffer)"},
+    }
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse_args(argv)
+    if args.steps < 1 and not args.dry_run:
+        print("bench.py: --steps must be at least 1", file=sys.stderr)
+        return 2
     world, rank, local = S.dist_env()
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         return launch_ranks(args, argv)
@@ -725,6 +843,28 @@ def main(argv=None):
     if pg:
         dist.barrier()
     elapsed = S.max_over_ranks(mine, device=dev)
+
+    # --dump-outputs: the last timed step's TX batch and status, before any later pass touches them
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, E, wl, (nstep[0] - 1) % R, rank, world)
+
+    if not args.full:
+        # A plain run ends here: the headline figure and what describes it.  Everything below this
+        # block (passes of their own after the timed region) is --full's.
+        per = gather_floats([rank, local, mine], device=dev)
+        if rank == 0:
+            out = headline(args, wl, world, elapsed, R, ramp_steps, ramp_ms, dist.get_backend() if pg else None)
+            out["per_rank"] = [{"rank": int(p[0]), "local_rank": int(p[1]), "elapsed_s": round(p[2], 6),
+                                "value": round(2 * wl.span_bytes * args.steps / p[2] / GIB, 2),
+                                "ms_per_step": round(p[2] / args.steps * 1e3, 4)} for p in per]
+            if dumped:
+                out["outputs"] = dumped
+            print(json.dumps(out), flush=True)
+        if pg:
+            dist.barrier()
+            dist.destroy_process_group()
+        return 0
 
     # Kernel durations for the roofline: K more steps with HIP events at the kernel boundaries, on
     # the stream the kernels are launched on.
@@ -847,7 +987,6 @@ def main(argv=None):
         parity = dict(parity or {}, spread=spread) if parity else {"spread": spread}
 
     if rank == 0:
-        value = S.aggregate_rate(2 * wl.span_bytes, world, args.steps, elapsed)
         # roofline of the dominant kernel: algorithmic bytes per launch / its mean launch time
         kernels = {
             "emit": {"ms": emit_ms, "bytes": wl.read_bytes + wl.desc_bytes + 4 * wl.n},
@@ -865,22 +1004,8 @@ def main(argv=None):
                      "value": round(2 * wl.span_bytes * args.steps / p[2] / GIB, 2),
                      "ms_per_step": round(p[2] / args.steps * 1e3, 4), "emit_ms": round(p[3], 4),
                      "verify_ms": round(p[4], 4), "verify_rejected": int(p[5])} for p in per]
-        out = {
-            "metric": METRIC,
-            "value": round(value, 2),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic: device-generated packets (splitmix64 payload, seeded), HBM-resident",
-            "config": {"workload": wl.workload, "records_per_gpu": wl.n, "parallelism": f"shard x{world} (no collective)",
-                       "checksummed_bytes_per_step_per_gpu": 2 * wl.span_bytes,
-                       "process_group": dist.get_backend() if pg else None},
+        out = headline(args, wl, world, elapsed, R, ramp_steps, ramp_ms, dist.get_backend() if pg else None)
+        out.update({
             "roofline": {"bound": "hbm", "kernel": f"{_launch_name(launched.get(dop))} ({dop})", "achieved": round(achieved, 1),
                          "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": round(achieved / HBM_PEAK_GBS, 4),
                          "traffic": traffic, "traffic_source": tsrc,
@@ -893,18 +1018,16 @@ def main(argv=None):
                                  for k, v in kernels.items()},
             "kernel_timing": "HIP events at the kernel boundaries on the launch stream, over a second pass of "
                              "K steps after the timed region (the timed region has no events between kernels)",
-            "ramp": {"steps": ramp_steps, "ms": round(ramp_ms, 1),
-                     "what": "untimed steps before the W warm-up steps until the GPU clocks have ramped "
-                             "(steady state: profiles/r03_steps/)"},
             "verify_rejected": rejected,
-            "batches": {"pairs": R, "what": (f"step i emits TX batch i mod {R} and verifies RX batch i mod {R} "
-                                             "(timed steps and kernel timings alike)") if R > 1 else
-                        "one batch (C5: emit and verify in place over one 201-GB buffer)"},
             "emit_same_batch": same_batch,
             "per_rank": per_rank,
             "cpu_baseline": cpu,
             "parity_sample": parity,
-        }
+        })
+        if R > 1:
+            out["batches"]["what"] += " (timed steps and kernel timings alike)"
+        if dumped:
+            out["outputs"] = dumped
         if probe:
             out["stream_read_probe"] = probe
         if floor and dom == "emit":

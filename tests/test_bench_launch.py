@@ -73,9 +73,9 @@ def test_host_cpu_share():
 
 @pytest.mark.gpu
 def test_bench_gpu_contract():
-    """The real GPU path of the launcher: `--gpus 1` on the box, the JSON contract of the line
-    (BASELINE.json's metric, n_gpus, per_rank, roofline with the emit floor, the clock ramp)."""
-    r = _run(["--gpus", "1", "--config", "c2", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0",
+    """The real GPU path of the launcher: `--gpus 1 --full` on the box, the JSON contract of the full
+    line (BASELINE.json's metric, n_gpus, per_rank, roofline with the emit floor, the clock ramp)."""
+    r = _run(["--gpus", "1", "--config", "c2", "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "0",
               "--ramp-ms", "50"], timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)
@@ -104,7 +104,7 @@ def test_bench_gpu_contract():
 def test_bench_c2copy_parity_spread():
     """C2copy's line carries the oracle check too: the fused copy-emit's TX bytes (payload and
     fields) over runs of records spread across the whole batch."""
-    r = _run(["--gpus", "1", "--config", "c2copy", "--steps", "3", "--warmup", "1", "--cpu-seconds", "0",
+    r = _run(["--gpus", "1", "--config", "c2copy", "--steps", "3", "--warmup", "1", "--full", "--cpu-seconds", "0",
               "--ramp-ms", "50"], timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     d = _json_line(r.stdout)

@@ -12,7 +12,7 @@ for rnd in $(seq 1 ${ROUNDS:-2}); do
         for i in "${!VS[@]}"; do
             v=${VS[$i]}
             echo "== $c [$v] round $rnd ($(date +%T))"
-            SMOLCSUM_LIB=$GRAFT_REPO_ROOT/smoltcp_amd/libsmolcsum_exp.so timeout -k 10 300 python bench.py --config $c --steps ${STEPS:-30} --warmup 5 --cpu-seconds 0 $v > $O/${c}_${i}_$rnd.log 2>&1 || { tail -20 $O/${c}_${i}_$rnd.log; exit 1; }
+            SMOLCSUM_LIB=$PWD/smoltcp_amd/libsmolcsum_exp.so timeout -k 10 300 python bench.py --full --config $c --steps ${STEPS:-30} --warmup 5 --cpu-seconds 0 $v > $O/${c}_${i}_$rnd.log 2>&1 || { tail -20 $O/${c}_${i}_$rnd.log; exit 1; }
             python3 - $O/${c}_${i}_$rnd.log <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -4,7 +4,7 @@ set -o pipefail
 cd "$GRAFT_REPO_ROOT"
 O=gpurun_out/cpub; mkdir -p $O
 for i in 1 2; do
-    timeout -k 10 250 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/c2_$i.json 2> $O/c2_$i.err || { tail -20 $O/c2_$i.err; exit 1; }
+    timeout -k 10 250 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $O/c2_$i.json 2> $O/c2_$i.err || { tail -20 $O/c2_$i.err; exit 1; }
 done
 python3 - <<'PY'
 import json

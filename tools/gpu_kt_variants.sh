@@ -8,7 +8,7 @@ mkdir -p $O
 for c in ${CFGS:-c2}; do
     for v in ${EMITV:-80}; do
         echo "== $c $v ($(date +%T))"
-        SMOLCSUM_LIB=$GRAFT_REPO_ROOT/smoltcp_amd/libsmolcsum_exp.so timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$c/$v -o run -- python3 bench.py --config $c --steps 20 --warmup 5 --cpu-seconds 0 --emit-variant $v > $O/${c}_$v.log 2>&1 || { tail -20 $O/${c}_$v.log; exit 1; }
+        SMOLCSUM_LIB=$PWD/smoltcp_amd/libsmolcsum_exp.so timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/$c/$v -o run -- python3 bench.py --full --config $c --steps 20 --warmup 5 --cpu-seconds 0 --emit-variant $v > $O/${c}_$v.log 2>&1 || { tail -20 $O/${c}_$v.log; exit 1; }
         f=$(find $O/$c/$v -name "*kernel_stats.csv" | head -1)
         python3 - "$f" <<'PY'
 import csv, sys

@@ -28,12 +28,12 @@ if [[ $S == *tests* ]]; then
 fi
 if [[ $S == *bench* ]]; then
     for c in ${BENCH:-c2 c3 c4 c2copy}; do
-        if [ $c = c2 ]; then step bench_c2 300 python bench.py --gpus 1 --steps 20 --warmup 5
-        else step bench_$c 300 python bench.py --config $c --cpu-seconds 0; fi
+        if [ $c = c2 ]; then step bench_c2 300 python bench.py --full --gpus 1 --steps 20 --warmup 5
+        else step bench_$c 300 python bench.py --full --config $c --cpu-seconds 0; fi
     done
 fi
 if [[ $S == *c5* ]]; then
-    step bench_c5 600 python bench.py --config c5 --steps 10 --warmup 2 --cpu-seconds 10
+    step bench_c5 600 python bench.py --full --config c5 --steps 10 --warmup 2 --cpu-seconds 10
 fi
 if [[ $S == *e2e* ]]; then
     step e2e 400 python tools/e2e.py
@@ -41,18 +41,18 @@ if [[ $S == *e2e* ]]; then
 fi
 if [[ $S == *kt* ]]; then
     for c in ${KT:-c2 c3 c4 c2copy}; do
-        step kt_$c 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof/$c/kt -o run -- python3 bench.py --config $c --steps 20 --warmup 5 --cpu-seconds 0
+        step kt_$c 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof/$c/kt -o run -- python3 bench.py --full --config $c --steps 20 --warmup 5 --cpu-seconds 0
     done
 fi
 if [[ $S == *pmc* ]]; then
     for c in ${PMC:-c2 c3 c4 c2copy}; do
-        step fetch_$c 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof/$c/fetch -o run -- python3 bench.py --config $c --steps 5 --warmup 1 --ramp-ms 0 --cpu-seconds 0
-        step write_$c 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof/$c/write -o run -- python3 bench.py --config $c --steps 5 --warmup 1 --ramp-ms 0 --cpu-seconds 0
+        step fetch_$c 120 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $O/prof/$c/fetch -o run -- python3 bench.py --full --config $c --steps 5 --warmup 1 --ramp-ms 0 --cpu-seconds 0
+        step write_$c 120 rocprofv3 --pmc WRITE_SIZE --output-format csv -d $O/prof/$c/write -o run -- python3 bench.py --full --config $c --steps 5 --warmup 1 --ramp-ms 0 --cpu-seconds 0
     done
 fi
 if [[ $S == *sq* ]]; then
     for c in ${SQ:-c2 c2copy}; do
-        step sq_$c 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_LDS --output-format csv -d $O/prof/$c/sq -o run -- python3 bench.py --config $c --steps 5 --warmup 1 --ramp-ms 0 --cpu-seconds 0
+        step sq_$c 120 rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_LDS --output-format csv -d $O/prof/$c/sq -o run -- python3 bench.py --full --config $c --steps 5 --warmup 1 --ramp-ms 0 --cpu-seconds 0
     done
 fi
 echo "== done ($(date +%T))"

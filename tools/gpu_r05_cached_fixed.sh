@@ -12,6 +12,6 @@ fi
 for i in 1 2; do
 for cv in ${BENCH:-c2:-1 c2:45 c2:63 c2:62 c4:-1 c4:45 c4:63}; do
     c=${cv%%:*}; v=${cv##*:}
-    SMOLCSUM_LIB=$EXP timeout -k 10 200 python -u bench.py --config $c --variant $v --steps 30 --warmup 5 --cpu-seconds 0 > $O/b_${c}_${v}_$i.json 2> $O/b_${c}_$v.err || { tail -5 $O/b_${c}_$v.err; exit 1; }
+    SMOLCSUM_LIB=$EXP timeout -k 10 200 python -u bench.py --full --config $c --variant $v --steps 30 --warmup 5 --cpu-seconds 0 > $O/b_${c}_${v}_$i.json 2> $O/b_${c}_$v.err || { tail -5 $O/b_${c}_$v.err; exit 1; }
 done
 done

@@ -13,5 +13,5 @@ fi
 SMOLCSUM_LIB=$EXP VARS=${DVARS:--1,62,63} CASES=${DCASES:-c3_packed,c3_gapped,c3_shuffled,short_packed,fixed1500} timeout -k 10 400 python -u tools/exp_r05_desc.py > $O/desc.jsonl 2>&1 || { tail -5 $O/desc.jsonl; exit 1; }
 for cv in ${BENCH:-c3:-1 c3:62 c3:63 c2:-1 c2:12 c2:14 c4:-1 c4:12}; do
     c=${cv%%:*}; v=${cv##*:}
-    SMOLCSUM_LIB=$EXP timeout -k 10 200 python -u bench.py --config $c --variant $v --steps 30 --warmup 5 --cpu-seconds 0 > $O/b_${c}_$v.json 2> $O/b_${c}_$v.err || { tail -5 $O/b_${c}_$v.err; exit 1; }
+    SMOLCSUM_LIB=$EXP timeout -k 10 200 python -u bench.py --full --config $c --variant $v --steps 30 --warmup 5 --cpu-seconds 0 > $O/b_${c}_$v.json 2> $O/b_${c}_$v.err || { tail -5 $O/b_${c}_$v.err; exit 1; }
 done

@@ -9,6 +9,6 @@ EXP=$PWD/smoltcp_amd/libsmolcsum_exp.so
 for i in 1 2; do
 for cv in $BENCH; do
     IFS=: read c e v <<< "$cv"
-    SMOLCSUM_LIB=$EXP timeout -k 10 200 python -u bench.py --config $c --emit-variant $e --verify-variant $v --steps 30 --warmup 5 --cpu-seconds 0 > $O/b_${c}_${e}_${v}_$i.json 2> $O/err || { tail -5 $O/err; exit 1; }
+    SMOLCSUM_LIB=$EXP timeout -k 10 200 python -u bench.py --full --config $c --emit-variant $e --verify-variant $v --steps 30 --warmup 5 --cpu-seconds 0 > $O/b_${c}_${e}_${v}_$i.json 2> $O/err || { tail -5 $O/err; exit 1; }
 done
 done

@@ -10,7 +10,7 @@ mkdir -p $O
 pass() {  # pass <name> <extra bench args> -- <counters...>
     local name=$1 extra=$2; shift 2
     echo "== $name ($(date +%T))"
-    timeout -k 10 120 rocprofv3 --pmc "$@" --output-format csv -d $O/$name -o run -- python3 bench.py --config c2copy --steps 5 --warmup 1 --ramp-ms 0 --cpu-seconds 0 $extra > $O/$name.log 2>&1 || { tail -20 $O/$name.log; exit 1; }
+    timeout -k 10 120 rocprofv3 --pmc "$@" --output-format csv -d $O/$name -o run -- python3 bench.py --full --config c2copy --steps 5 --warmup 1 --ramp-ms 0 --cpu-seconds 0 $extra > $O/$name.log 2>&1 || { tail -20 $O/$name.log; exit 1; }
 }
 pass rd "" TCC_EA0_RDREQ_sum TCC_EA0_RDREQ_32B_sum TCC_EA0_RDREQ_64B_sum
 pass wr "" TCC_EA0_WRREQ_sum TCC_EA0_WRREQ_64B_sum

@@ -20,7 +20,7 @@ fi
 for rnd in 1 2; do
     for c in ${AB:-c2 c4}; do
         for v in ${EMITV:-80 81 57 -1}; do
-            SMOLCSUM_LIB=$GRAFT_REPO_ROOT/smoltcp_amd/libsmolcsum_exp.so step ab_${c}_${v}_$rnd 300 python bench.py --config $c --steps 30 --warmup 5 --cpu-seconds 0 --emit-variant $v
+            SMOLCSUM_LIB=$PWD/smoltcp_amd/libsmolcsum_exp.so step ab_${c}_${v}_$rnd 300 python bench.py --full --config $c --steps 30 --warmup 5 --cpu-seconds 0 --emit-variant $v
         done
     done
 done

@@ -15,14 +15,14 @@ step() {  # step <name> <seconds> <cmd...>: stop on the first failure
     tail -${TAILN:-1} "$O/$name.log" | cut -c1-400
 }
 for i in 1 2 3; do
-    step drv_$i 200 python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0
+    step drv_$i 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0
 done
-step w100 200 python bench.py --gpus 1 --steps 20 --warmup 100 --cpu-seconds 0
-step s200 200 python bench.py --gpus 1 --steps 200 --warmup 5 --cpu-seconds 0
-step kt_drv 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt_drv -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0
-step kt_w100 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt_w100 -o run -- python3 bench.py --gpus 1 --steps 20 --warmup 100 --cpu-seconds 0
+step w100 200 python bench.py --full --gpus 1 --steps 20 --warmup 100 --cpu-seconds 0
+step s200 200 python bench.py --full --gpus 1 --steps 200 --warmup 5 --cpu-seconds 0
+step kt_drv 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt_drv -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0
+step kt_w100 300 rocprofv3 --kernel-trace --output-format csv -d $O/kt_w100 -o run -- python3 bench.py --full --gpus 1 --steps 20 --warmup 100 --cpu-seconds 0
 if [ -n "$C5" ]; then
-    step c5 600 python bench.py --config c5 --steps 10 --warmup 2 --cpu-seconds 10
-    step kt_c5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c5 -o run -- python3 bench.py --config c5 --steps 10 --warmup 2 --cpu-seconds 0
+    step c5 600 python bench.py --full --config c5 --steps 10 --warmup 2 --cpu-seconds 10
+    step kt_c5 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/kt_c5 -o run -- python3 bench.py --full --config c5 --steps 10 --warmup 2 --cpu-seconds 0
 fi
 echo "== done ($(date +%T))"

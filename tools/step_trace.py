@@ -1,10 +1,10 @@
 #!/usr/bin/env python3
 """Per-step timeline of a `bench.py` run from a rocprofv3 kernel trace.
 
-    rocprofv3 --kernel-trace --output-format csv -d DIR -o run -- python3 bench.py --steps K --warmup W --cpu-seconds 0
+    rocprofv3 --kernel-trace --output-format csv -d DIR -o run -- python3 bench.py --full --steps K --warmup W --cpu-seconds 0
     python tools/step_trace.py DIR --steps K --warmup W [--out profiles/r03_step_trace_c2.json]
 
-bench.py launches, after the workload set-up, the clock-ramp steps, W warm-up steps, the K timed
+bench.py --full launches, after the workload set-up, the clock-ramp steps, W warm-up steps, the K timed
 steps and K more steps with HIP events (the kernel-duration pass), each step = one emit (or
 copy-emit) + one verify; then the probes (stream_read_kernel first) and one more emit.  The last 4K
 checksum launches before the first probe kernel are therefore the timed and the event pass, and
