@@ -127,10 +127,33 @@ int smol_csum_tool_field_scatter(smol_csum_ctx_t* ctx, uint8_t* d_buf, uint64_t 
 /* The launch shape the library picks for a verify over an implicit batch of `len`-byte records. */
 int smol_csum_tool_auto_shape(uint32_t len, int has_desc);
 
+/* The dispatch decision, without a context or a device: what a batched call of `op` (0 data, 1 emit,
+ * 2 verify, 3 copy-emit) on `batch` runs when the context forces `variant` (-1: none; SMOL_EINVAL when
+ * this library does not build it) and `shape` (-1: none) and its descriptor-emit choice is `desc_staged`;
+ * `nhc` non-zero: through the 6LoWPAN NHC UDP entry points.  out = {family, variant, shape}: family
+ * 0 csum_kernel, 1 csum_tile_kernel, 2 xwalk_kernel, 3 dwalk_kernel, 4 the stripe kernel, 5 copy_kernel,
+ * 6 xcopy_kernel; shape -1 where the family has none.  Nothing in the batch is dereferenced (a
+ * non-null `desc` only marks a descriptor batch).  The one dispatch function the batched entry points
+ * call (csum_dispatch.h pick_kernel). */
+int smol_csum_tool_pick(int variant, int shape, int desc_staged, int op, const smol_csum_batch_t* batch, int nhc,
+                        int out[3]);
+/* The registry's row of a variant number (csrc/variants.def), in this library or not:
+ * out = {family, flags (1 copy-only, 2 walk-kernel copy form, 4 line grid, 8 16 x 4 over descriptors,
+ * 16 staged emit, 32 no stores: wrong bytes by design, 64 NHC batches run the line-grid NHC kernel),
+ * built in this library, experiments-only}.
+ * SMOL_EINVAL: the number has no row. */
+int smol_csum_tool_variant_info(int variant, int out[4]);
+/* The kernel form a transposed-walk or descriptor-walk variant built in this library runs for `op`
+ * (1 emit, 2 verify): out[0] = family, then for xwalk_kernel {NOSTORE, SEG, PERSIST, NTS, HALF, STAGE,
+ * HINT, WPE, WV, STEPS, ONLY_R, MAX_LEN (0: any)}, for dwalk_kernel {NOSTORE, GROUPS, SEGF, SEGPASS}
+ * (the rest 0).  Read through the switch the launchers instantiate their kernels with.  SMOL_EINVAL: not
+ * such a variant, or it has no form of that op. */
+int smol_csum_tool_form(int variant, int op, int out[13]);
+
 /* The kernel (the rocprofv3 name prefix: "csum_kernel", "csum_tile_kernel", "xwalk_kernel",
  * "dwalk_kernel", "copy_kernel" or "xcopy_kernel") that an IP-path operation on `batch` runs with this
- * context's variant setting: op 0 data, 1 emit, 2 verify, 3 copy-emit.  The same choice as the
- * batched entry points make (one dispatch function, csum_api.cpp pick_kernel). */
+ * context's variant setting: op 0 data, 1 emit, 2 verify, 3 copy-emit (smol_csum_tool_pick with the
+ * context's settings). */
 const char* smol_csum_tool_kernel_for(const smol_csum_ctx_t* ctx, int op, const smol_csum_batch_t* batch);
 /* Deprecated (kept for old scripts): smol_csum_tool_kernel_for without the batch, so without its record
  * length — exact for descriptor batches; for fixed-stride batches it names the kernel of short records,
@@ -146,7 +169,8 @@ uint32_t smol_csum_tool_last_launch(void);
 
 /* 1 when this build of the library runs kernel variant `variant` (smol_csum_tool_set_variant), else
  * 0.  The product library carries the defaults and one fallback per operation; the experiments
- * build (`make -C smoltcp_amd/csrc EXP=1`, libsmolcsum_exp.so) every measured variant. */
+ * build (`make -C smoltcp_amd/csrc EXP=1`, libsmolcsum_exp.so) every measured variant: the number has a
+ * row in csrc/variants.def, and the row is built in this library. */
 int smol_csum_tool_variant_built(int variant);
 
 #ifdef __cplusplus

@@ -43,10 +43,12 @@ TOOL_SYMBOLS = [
     "smol_csum_tool_field_probe_list", "smol_csum_tool_segment_probe", "smol_csum_tool_field_scatter",
     "smol_csum_tool_variant_built",
     "smol_csum_tool_kernel_name", "smol_csum_tool_kernel_for", "smol_csum_tool_last_launch",
+    "smol_csum_tool_pick", "smol_csum_tool_variant_info", "smol_csum_tool_form",
 ]
 # Tool symbols added in later rounds: bound only when the loaded build has them (SMOLCSUM_LIB may name
 # an older build for an A/B run), and a call to a missing one raises AttributeError naming it.
-OPTIONAL_TOOL_SYMBOLS = ("smol_csum_tool_variant_built", "smol_csum_tool_kernel_for", "smol_csum_tool_segment_probe")
+OPTIONAL_TOOL_SYMBOLS = ("smol_csum_tool_variant_built", "smol_csum_tool_kernel_for", "smol_csum_tool_segment_probe",
+                         "smol_csum_tool_pick", "smol_csum_tool_variant_info", "smol_csum_tool_form")
 
 
 class SmolError(RuntimeError):
@@ -163,15 +165,19 @@ def lib(path: str | None = None) -> ctypes.CDLL:
     L.smol_csum_tool_kernel_name.restype = ctypes.c_char_p
     L.smol_csum_tool_last_launch.argtypes = []
     L.smol_csum_tool_last_launch.restype = u32
-    if hasattr(L, "smol_csum_tool_variant_built"):
-        L.smol_csum_tool_variant_built.argtypes = [i32]
-        L.smol_csum_tool_variant_built.restype = i32
-    if hasattr(L, "smol_csum_tool_segment_probe"):
-        L.smol_csum_tool_segment_probe.argtypes = [vp, vp, u64, vp, ctypes.c_int, vp]
-        L.smol_csum_tool_segment_probe.restype = i32
-    if hasattr(L, "smol_csum_tool_kernel_for"):
-        L.smol_csum_tool_kernel_for.argtypes = [vp, i32, vp]
-        L.smol_csum_tool_kernel_for.restype = ctypes.c_char_p
+    optional = {
+        "smol_csum_tool_variant_built": ([i32], i32),
+        "smol_csum_tool_segment_probe": ([vp, vp, u64, vp, ctypes.c_int, vp], i32),
+        "smol_csum_tool_kernel_for": ([vp, i32, vp], ctypes.c_char_p),
+        "smol_csum_tool_pick": ([i32, i32, i32, i32, ctypes.POINTER(BatchC), i32, ctypes.POINTER(i32)], i32),
+        "smol_csum_tool_variant_info": ([i32, ctypes.POINTER(i32)], i32),
+        "smol_csum_tool_form": ([i32, i32, ctypes.POINTER(i32)], i32),
+    }
+    assert set(optional) == set(OPTIONAL_TOOL_SYMBOLS)
+    for name in OPTIONAL_TOOL_SYMBOLS:
+        if hasattr(L, name):
+            f = getattr(L, name)
+            f.argtypes, f.restype = optional[name]
     _LIBS[path] = L
     return L
 

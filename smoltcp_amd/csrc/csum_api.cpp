@@ -11,7 +11,7 @@
 
 #include "../../include/smolcsum.h"
 #include "../../include/smolcsum_tools.h"
-#include "csum_launch.h"
+#include "csum_dispatch.h"
 
 using namespace smolcsum;
 
@@ -20,14 +20,14 @@ struct smol_csum_ctx {
     int num_cu;
     uint32_t max_blocks;  // grid cap (kNaturalGrid: one work item per group)
     int shape;            // -1 automatic, else CFG_*
-    int variant;          // kernel variant (-1 automatic; csum_walk.h VarT, 3/4 tile kernel)
+    int variant;          // kernel variant (-1 automatic; variants.def)
     uint8_t* dummy;       // 256 zero bytes on the device (target of loads with nothing to read)
     int tile_records;     // tile kernel: records per wavefront tile (32 or 64)
     bool max_blocks_set;  // grid cap given explicitly (tooling)
     int xcd_remap;        // walk kernel: each XCD's blocks take a contiguous range of records
                           // (-1: automatic, xcd_remap_auto; 0 / 1: forced, tooling)
     uint64_t launch_records;  // records per kernel launch (0: the whole batch in one launch)
-    // staged emit (variant 94; 80 / 81 experiments): the field entries and per-8-record flags of one
+    // staged emit (the registry's V_STAGED variants): the field entries and per-8-record flags of one
     // chunk of kStageChunk records, allocated with the context (no allocation in a batched call);
     // stage_stream / stage_done order a staged emit on another stream after the previous one
     uint64_t* stage;
@@ -35,7 +35,8 @@ struct smol_csum_ctx {
     void* stage_stream;
     bool stage_recorded;
     hipEvent_t stage_done;
-    // descriptor-batch emit chooses between the staged form (97) and the in-place one (41) from the
+    // descriptor-batch emit chooses between the staged form (kDwalkEmitStaged) and the in-place one
+    // (kDwalkEmit) from the
     // previous staged call's wavefront flags (a sample of the first kSample copied to host memory):
     // staged while at least half of the sampled wavefronts staged, else in place, probing with the
     // staged form again every kReprobe calls
@@ -99,146 +100,6 @@ bool caps_valid(const smol_checksum_caps_t* c) {
 // 0.244 ms vs 0.27 ms at 8 blocks per CU).
 constexpr uint32_t kNaturalGrid = 0x7fffffffu;
 
-// Kernel variant when none is forced (tools/sweep.py on MI355X, C2 / C3 / C4): the 128-byte line
-// grid with non-temporal loads (verify: C2 0.2415 -> 0.2327 ms, C4 0.2158 -> 0.2083 ms, C3 0.826 ->
-// 0.815 ms; fixed-stride emit with shared boundary lines, csum_walk.h shared_from: C2 0.3155 ->
-// 0.304 ms, C4 0.2727 -> 0.263 ms), except emit over descriptor batches: the tile kernel on the
-// line grid (variant 7, C3 0.9285 ms vs the walk kernel's best 0.9945 ms at the same shape; its
-// verify is slower, 1.08 ms vs 0.83 ms).  walk_variant is the walk kernel's own choice, for the
-// entry points the tile kernel does not serve (NHC, data, copy-emit): cached loads on the 16-byte
-// grid for emit over descriptors (C3 0.9705 ms vs 0.9722 ms), the line grid otherwise.
-// Verify over descriptor batches (C3) runs the line grid without the register prefetch (variant
-// 13) at 16 x 4: with the record geometry in LDS that kernel holds 63 VGPRs (8 waves/SIMD), and the
-// waves hide the latency the prefetch hid before: C3 verify 0.7998 ms (variant 5, 16 x 3) ->
-// 0.7425 ms (tools/gpu_ab.sh, MI355X).  Fixed-stride verify keeps the prefetch (C2 8 x 7: 0.2378
-// vs 0.2519 ms without).
-int walk_variant(int mode, bool has_desc) {
-    // fixed-stride emit: variant 5 with the fields' 64-B segments written whole where no neighbour's
-    // field shares them (C2 emit 0.305 -> 0.294 ms, tools/exp_emit_seg.py), skipped on wavefronts
-    // without an IPv4 record (variant 29: C2 0.2891-0.2894 vs 19's 0.2907-0.2913 ms, C4 0.2649-0.2658
-    // vs 0.2654-0.2666 ms, interleaved on one box, profiles/r04_experiments/).  Round 5: variant 39
-    // = 29, and on a wavefront without an IPv4 record whole segments for IPv6 records too, decided
-    // by one ballot (bench lines over rotating batches, interleaved on one box,
-    // profiles/r05_experiments/emit_variants_bench.txt: C4 5151-5157 -> 5237-5253 GiB/s, C2 equal)
-    if (!has_desc) return mode == MODE_EMIT ? 39 : 5;
-    return mode == MODE_EMIT ? 1 : mode == MODE_VERIFY ? 13 : 5;
-}
-// Round 5: verify over descriptor batches runs dwalk_kernel's per-group walk (csum_dwalk.hip: 8
-// records per wavefront, parse first, 8 lanes x 4 chunks per step on the line grid, 7 waves / SIMD):
-// C3 0.793 -> 0.742 ms, 64-1500-B records 0.343 -> 0.185 ms with non-temporal header windows
-// (variant 60, tools/exp_r05_desc.py, profiles/r05_experiments/dwalk_layouts.jsonl).  Variant 63
-// loads the header windows with the default cache policy, so that the stream's second read of those
-// lines and emit's field stores hit the L2: C3 bench (4 batch pairs in turn, one box, interleaved)
-// verify 0.742 -> 0.731 ms and emit 0.942 (tile 7) -> 0.896 ms, 5269 -> 5457 GiB/s
-// (profiles/r05_experiments/dwalk_cached_windows.txt); its emit beats the tile kernel on every
-// descriptor layout measured, 64-1500-B records 0.223 -> 0.184 ms.  The tile kernel stays the
-// descriptor-emit fallback (NHC emit runs the walk kernel).
-// Its emit form 41 sums the 16 window chunks from LDS and streams from chunk 16 (the window lines not
-// read a second time): C3 emit 0.894 -> 0.881 ms, shuffled descriptors 0.922 -> 0.912, 64-1500-B
-// records 0.186 -> 0.183; its verify measured 0.4 % slower, so verify stays on 63
-// (profiles/r05_experiments/dwalk_cached_windows.txt).
-int auto_variant(int mode, bool has_desc) {
-    if (mode == MODE_EMIT && has_desc) return 41;
-    if (mode == MODE_VERIFY && has_desc) return 63;
-    return walk_variant(mode, has_desc);
-}
-
-// The transposed walk (csum_xwalk.hip) for fixed-stride records where it beats the walk kernel, from a
-// measured table (round 6; VERDICT r05 item 7 replaced round 5's fitted length windows): one length
-// sweep, tools/sweep_dispatch.py, over 1024 .. 9023 B in steps of 64 B (multiples of 64, + 28, and + 28
-// with 64-B gaps), verify and emit (emit in bench.py's step order), on three boxes
-// (profiles/r06_dispatch_sweep_box{1,2,3}.jsonl), turned into dispatch_table.inc by
-// tools/gen_dispatch_table.py (the least summed time per entry).  Verify: the walk kernel (5), the
-// transposed walk (47) or 47 with the first-load hint (89: lanes 0-3 of each record's first instruction
-// with the default cache policy; C2 verify 0.2342 -> 0.2259 ms); emit: the walk kernel (39), 47, 57 (47
-// with non-temporal field segments) or 101 (57's segments stored write-through), from a second emit
-// sweep that ran all four (late round 6, profiles/r06_dispatch_sweep_wt_*.jsonl: two IPv4 boxes, two
-// IPv6-mix boxes; C2's and C4's rows take 101).  Outside 1024 .. 9023 B the walk kernel
-// (round 5: past 9000 B the two trade places by length, within 2 %).
-// Returns the transposed-walk variant to run (0: the walk kernel).
-#include "dispatch_table.inc"
-
-int xwalk_auto(int mode, const smol_csum_batch_t* b) {
-    if (b->desc || b->stride < b->len || (mode != MODE_VERIFY && mode != MODE_EMIT)) return 0;
-    if (b->len < 1024 || b->len >= 1024 + 64 * 125) return 0;
-    const uint32_t k = (b->len - 1024) / 64;
-    const int col = b->stride != b->len ? 2 : (b->len % 64 == 0 ? 0 : 1);
-    const char c = (mode == MODE_VERIFY ? kVerifyTable : kEmitTable)[k][col];
-    if (mode == MODE_VERIFY) return c == 'h' ? 89 : c == 'x' ? 47 : 0;
-    return c == 't' ? 101 : c == 'n' ? 57 : c == 'x' ? 47 : 0;
-}
-
-// The XCD block order (csum_launch.h xcd_block / xcd_chunk) when none is forced: the contiguous order
-// for fixed-stride emit over at least 4 GiB.  Measured per 2^20 C2 records (tools/exp_inplace.py, one box,
-// profiles/r04_experiments/xcd_remap.jsonl): emit 0.327 -> 0.298 ms at 2^22 records (6.3 GB),
-// 0.332 -> 0.320 at 2^24, 0.338 -> 0.303 at 2^26, and C5's 2^27: 0.334 -> 0.300; at 2^20 records
-// 0.297 -> 0.2995 (no gain).  Verify runs 4-6 % slower with it at every size, so it keeps the
-// dispatch order.
-// Verify over at least 64 GiB takes runs of 256 workgroups per XCD turn: C5's in-place verify 31.38-
-// 31.46 -> 30.96-30.99 ms (profiles/r04_experiments/c5_verify_grain.jsonl); at 25 GB it was +1 %,
-// at 100 GB -0.6 % (xcd_grain.jsonl), so smaller batches keep the dispatch order.
-int xcd_remap_auto(int mode, const smol_csum_batch_t* b) {
-    if (b->desc) return 0;
-    const uint64_t bytes = b->n * b->stride;
-    if (mode == MODE_EMIT) return bytes >= (4ull << 30) ? 1 : 0;
-    if (mode == MODE_VERIFY) return bytes >= (64ull << 30) ? 256 : 0;
-    return 0;
-}
-
-// SMOL_BATCH_FIELD_STORES: the same kernel without the whole-segment writes (2-B field stores only).
-int field_store_variant(int variant, bool has_desc) {
-    if (variant == 19 || variant == 23 || variant == 24 || variant == 25 || variant == 29 || variant == 39) return 5;
-    if (variant == 47 || variant == 57 || variant == 45 || (variant >= 80 && variant <= 93) || variant == 99 || variant == 100 ||
-        variant == 101)
-        return 44;
-    if (variant == 61) return 60;  // the descriptor walk's emit: 2-B stores (62: cached windows, 63)
-    if (variant == 62 || variant == 18) return 63;  // (63 stores 2-B fields only)
-    if (variant == 20) return 60;
-    if (variant == 41 || (variant >= 94 && variant <= 97) || (variant >= 103 && variant <= 105) || variant == 109) return 41;
-    if (variant == 26 || variant == 27 || variant == 28) return 13;
-    return variant;
-}
-
-// The kernel variants this build runs (smol_csum_tool_variant_built).  The product library: the
-// defaults (walk 5 / 39, transposed walk 47 / 57, descriptor walk 63 (verify) / 41 (emit), copy 21)
-// and one fallback each (descriptor walk 60, tile 7, copy 17; walk 13 for NHC / data over
-// descriptors and for forced variants; 44 = 47 / 57 with 2-B field stores, SMOL_BATCH_FIELD_STORES).  The experiments build (SMOL_EXP, libsmolcsum_exp.so): every measured variant.
-bool variant_built(int v) {
-    switch (v) {
-        case -1: case 5: case 7: case 13: case 17: case 21: case 39: case 41: case 44: case 47: case 57: case 60: case 63:
-        case 89: case 97: case 101: return true;
-        default: break;
-    }
-#ifdef SMOL_EXP
-    if ((v >= 80 && v <= 96 && v != 89) || (v >= 98 && v <= 100) || (v >= 102 && v <= 110) || v == 112 || v == 113) return true;
-    const int b = v >= 64 ? v - 64 : v;
-    if (v >= 64) return b == 5 || b == 29 || (b >= 31 && b <= 39) || b == 44 || b == 47 || b == 56 || b == 61;
-    return (v >= 0 && v <= 4) || v == 6 || (v >= 8 && v <= 11) || v == 16 || v == 19 || (v >= 23 && v <= 29) ||
-           (v >= 31 && v <= 38) || v == 40 || v == 12 || v == 14 || v == 42 || v == 43 || v == 45 || v == 46 || v == 15 || v == 18 || v == 20 || v == 22 || v == 30 || v == 41 || v == 48 || (v >= 49 && v <= 59) || v == 61 || v == 62;
-#else
-    return false;
-#endif
-}
-
-bool line_grid(int variant) {
-    if (variant >= 64) variant -= 64;  // experiment variants without stores
-    if ((variant >= 31 && variant <= 40) || variant == 12 || variant == 14) return true;
-    return variant == 5 || variant == 6 || variant == 9 || variant == 10 || variant == 13 || variant == 19 ||
-           (variant >= 23 && variant <= 29);
-}
-
-int auto_shape(uint32_t len, bool has_desc, bool line = false, int variant = -1) {
-    if (has_desc) return (variant == 13 || variant == 26 || variant == 27 || variant == 28) ? CFG_G16U4 : CFG_G16U3;
-    const uint64_t need = (uint64_t)len + (line ? 127 : 15);  // bytes of aligned chunks a record can touch
-    // eight records per wavefront in two steps, with as few idle lanes as possible (C4's 1320-B
-    // records on the line grid: 8 x 6 0.2083 ms, 8 x 7 0.2188 ms; C2's 1500 B: 8 x 7 0.2327 ms)
-    if (need <= 16 * 8 * 6 * 2) return CFG_G8U6;
-    if (line && need <= 16 * 8 * 7 * 2) return CFG_G8U7;
-    if (need <= 16 * 16 * 6) return CFG_G16U6;
-    if (need <= 16 * 32 * 4) return CFG_G32U4;
-    return CFG_G64U4;
-}
-
 int check_batch(const smol_csum_batch_t* b, const void* d_buf) {
     if (!b) return SMOL_EINVAL;
     if (b->n == 0) return SMOL_OK;
@@ -254,93 +115,10 @@ int check_batch(const smol_csum_batch_t* b, const void* d_buf) {
     return SMOL_OK;
 }
 
-// The kernel a batched call runs: its family, variant and (walk / tile / copy kernels) launch shape.
-// One pure function, so that smol_csum_tool_kernel_for names exactly what run() launches.
-enum Family { F_WALK, F_TILE, F_XWALK, F_DWALK, F_STRIPE, F_COPY, F_XCOPY };
-struct Pick {
-    int family;
-    int variant;
-    int shape;
-};
+PickCtx pick_ctx(const smol_csum_ctx_t* ctx) { return {ctx->variant, ctx->shape, ctx->desc_staged}; }
 
-// Variants that serve copy-emit only: copy_kernel (17, 21; 22 / 30 experiments), the transposed
-// layout (49-55, experiments) and the walk kernel's MODE_COPY forms 8 / 11 / 16 (experiments).  Forced
-// on a context, they leave emit / verify / data to the library's choice (the automatic dispatch).
-bool copy_only(int v) { return v == 8 || v == 11 || v == 16 || v == 17 || v == 21 || v == 22 || v == 30 || v == 98 || v == 102 || (v >= 49 && v <= 55); }
-
-Pick pick_kernel(const smol_csum_ctx_t* ctx, int mode, const smol_csum_batch_t* b, const KParams& p) {
-    const bool has_desc = b->desc != nullptr;
-    const bool nhc = p.addrs != nullptr;
-    if (mode == MODE_COPY) {  // one fused pass (no tile / deferred variants)
-        // default: variant 21 (csum_copy.hip: variant 17's body chunks = one source load + shift +
-        // sum + store, with the first body round's loads issued ahead of round 1's stores) at its
-        // default shape (16 x 4): C2copy 0.772-0.853 ms (variant 16) -> 0.692 ms (17) -> 0.678 ms
-        // (21; tools/exp_copy.py, MI355X).  Variants 1 / 8 / 11 / 16 / 17 stay selectable.
-        const int cv = ctx->variant;
-        if (cv >= 49 && cv <= 55 && xcopy_fits(p)) return {F_XCOPY, cv, -1};
-        const int var = (cv == 1 || cv == 8 || cv == 11 || cv == 16 || cv == 17 || cv == 22 || cv == 30 || cv == 98 || cv == 102) ? cv : 21;
-        const bool ck = var == 17 || var == 21 || var == 22 || var == 30 || var == 98 || var == 102;
-        const int gv = cv >= 0 ? cv : walk_variant(mode, has_desc);
-        const int shape = ctx->shape >= 0 ? ctx->shape : ck ? (int)CFG_G16U4 : auto_shape(b->len, has_desc, line_grid(gv), gv);
-        return {ck ? F_COPY : F_WALK, var, shape};
-    }
-    int variant = copy_only(ctx->variant) ? -1 : ctx->variant;
-    if (variant < 0) {
-        const int xv = nhc ? 0 : xwalk_auto(mode, b);
-        variant = xv ? xv : auto_variant(mode, has_desc);
-        // descriptor-batch emit: the staged form while the records stage (see smol_csum_ctx)
-        if (variant == 41 && ctx->desc_staged) variant = 97;
-    }
-    if (mode == MODE_EMIT && (b->flags & SMOL_BATCH_FIELD_STORES)) variant = field_store_variant(variant, has_desc);
-    // a kernel that does not serve the batch falls back to the default of its kind (descriptor emit:
-    // the tile kernel; otherwise the walk kernel)
-    const int fallback = (mode == MODE_EMIT && has_desc && !nhc) ? 7 : walk_variant(mode, has_desc);
-    // the stripe kernel (variant 42, experiments): emit / verify of packed fixed-stride 1024-1520-B records
-    if (variant == 42) {
-        if ((mode == MODE_EMIT || mode == MODE_VERIFY) && !nhc && stripe_fits(p)) return {F_STRIPE, 42, -1};
-        variant = fallback;
-    }
-    // the transposed walk (44 / 47 / 57 product, the others experiments): fixed-stride records of
-    // 1024 - 16257 B
-    const int v64 = variant % 64;
-    const bool xw_var = (variant < 64 && (variant == 44 || variant == 47 || variant == 43 || variant == 45 || variant == 46 ||
-                                          variant == 15 || variant == 48 || variant == 57 || variant == 58 || variant == 59)) ||
-                        (variant >= 64 && (v64 == 44 || v64 == 47)) || staged_variant(variant) || (variant >= 82 && variant <= 93) ||
-                        variant == 99 || variant == 100 || variant == 101 || variant == 106 || variant == 107 || variant == 108 || variant == 110 || variant == 112 || variant == 113;
-    if (xw_var) {
-        if ((mode == MODE_EMIT || mode == MODE_VERIFY) && !nhc && xwalk_fits(p)) return {F_XWALK, variant, -1};
-        variant = fallback;
-    }
-    // descriptor-batch walks: 63 = verify default (cached header windows), 41 = emit default (its emit
-    // form), 60 = the non-temporal-window verify; 56, 60's emit, 61 / 62 (whole field segments) and
-    // 18 / 20 (non-temporal 2-B fields) in the experiments build, which also runs them forced over
-    // fixed-stride batches
-    if (mode == MODE_VERIFY) {
-        if (variant == 41 || variant == 18 || variant == 62 || (variant >= 94 && variant <= 97) || (variant >= 103 && variant <= 105) || variant == 109) variant = 63;  // emit forms of 63
-        if (variant == 20 || variant % 64 == 61) variant = 60;              // emit forms of 60
-    }
-#ifdef SMOL_EXP
-    const bool dw_var = variant % 64 == 56 || variant == 60 || variant % 64 == 61 || variant == 62 || variant == 63 ||
-                        variant == 18 || variant == 20 || variant == 41 || (variant >= 94 && variant <= 97) || (variant >= 103 && variant <= 105) || variant == 109;
-    const bool dw_ok = (mode == MODE_EMIT || mode == MODE_VERIFY) && !nhc;
-#else
-    const bool dw_var = variant == 60 || variant == 63 || variant == 41 || variant == 97;
-    const bool dw_ok = (mode == MODE_VERIFY || (mode == MODE_EMIT && variant != 60)) && has_desc && !nhc;
-#endif
-    if (dw_var) {
-        if (dw_ok) return {F_DWALK, variant, -1};
-        variant = fallback;
-    }
-    // the tile kernel (3 / 4 / 7: nt / plain / nt on the line grid): IP emit and verify only
-    const bool tile_var = variant == 3 || variant == 4 || variant == 7;
-    if (tile_var && (mode == MODE_DATA || nhc)) variant = walk_variant(mode, has_desc);
-    const int shape = ctx->shape >= 0 ? ctx->shape : auto_shape(b->len, has_desc, line_grid(variant), variant);
-    if (variant == 3 || variant == 4 || variant == 7) return {F_TILE, variant, shape};
-    return {F_WALK, variant, shape};
-}
-
-const char* family_kernel(const Pick& k) {
-    switch (k.family) {
+const char* family_kernel(int family) {
+    switch (family) {
         case F_TILE: case F_STRIPE: return "csum_tile_kernel";
         case F_XWALK: return "xwalk_kernel";
         case F_DWALK: return "dwalk_kernel";
@@ -439,9 +217,8 @@ int run(smol_csum_ctx_t* ctx, int mode, uint8_t* d_buf, const smol_csum_batch_t*
     }
     const bool desc_auto = mode == MODE_EMIT && has_desc_auto(ctx, b, d_addrs);
     if (desc_auto) update_desc_choice(ctx, s);
-    const Pick k = pick_kernel(ctx, mode, b, p);
-    if (mode == MODE_EMIT && ((k.family == F_XWALK && staged_variant(k.variant)) ||
-                              (k.family == F_DWALK && staged_desc_variant(k.variant)))) {
+    const Pick k = pick_kernel(pick_ctx(ctx), mode, b, p);
+    if (mode == MODE_EMIT && variant_is(k.variant, V_STAGED)) {
         // staged emit: kStageChunk records at a time through the context's entries, each chunk's staging
         // launch followed by its segment pass.  A call on another stream than the previous staged emit
         // first waits for that one (the entries are the context's).
@@ -474,7 +251,7 @@ int run(smol_csum_ctx_t* ctx, int mode, uint8_t* d_buf, const smol_csum_batch_t*
         case F_XWALK: e = launch_xwalk(mode, k.variant, p, s); break;
         case F_STRIPE: e = launch_stripe(mode, p, s); break;
         case F_TILE:
-            e = launch_tile(mode, k.shape, k.variant == 7 ? 2 : k.variant - 3, ctx->tile_records, p, ctx->max_blocks, s);
+            e = launch_tile(mode, k.shape, find_variant(k.variant)->tile_loads, ctx->tile_records, p, ctx->max_blocks, s);
             break;
         default: e = launch_csum(mode, k.shape, k.variant, p, ctx->max_blocks, s); break;  // walk / copy kernels
     }
@@ -807,10 +584,9 @@ int smol_csum_tool_field_scatter(smol_csum_ctx_t* ctx, uint8_t* d_buf, uint64_t 
 }
 
 int smol_csum_tool_auto_shape(uint32_t len, int has_desc) {
-    // the walk kernel's verify shape (descriptor batches: its variant 13, which serves them when the
+    // the walk kernel's verify shape (descriptor batches: kWalkVerifyDesc, which serves them when the
     // descriptor walk does not: NHC, data, forced variants)
-    const int v = has_desc ? walk_variant(MODE_VERIFY, true) : auto_variant(MODE_VERIFY, false);
-    return auto_shape(len, has_desc != 0, line_grid(v), v);
+    return auto_shape(len, has_desc != 0, walk_variant(MODE_VERIFY, has_desc != 0));
 }
 
 const char* smol_csum_tool_kernel_name(const smol_csum_ctx_t* ctx, int op, int has_desc) {
@@ -826,15 +602,56 @@ const char* smol_csum_tool_kernel_name(const smol_csum_ctx_t* ctx, int op, int h
     return smol_csum_tool_kernel_for(ctx, op, &b);
 }
 
-const char* smol_csum_tool_kernel_for(const smol_csum_ctx_t* ctx, int op, const smol_csum_batch_t* b) {
-    if (!ctx || !b || op < MODE_DATA || op > MODE_COPY) return "";
-    KParams p;
+int smol_csum_tool_pick(int variant, int shape, int desc_staged, int op, const smol_csum_batch_t* b, int nhc, int out[3]) {
+    if (!b || !out || op < MODE_DATA || op > MODE_COPY || !variant_built(variant) || shape < -1 || shape >= CFG_COUNT)
+        return SMOL_EINVAL;
+    KParams p;  // what the dispatch reads of the launch parameters: the batch form (nothing dereferenced)
     std::memset(&p, 0, sizeof p);
     p.desc = b->desc;
     p.n = b->n;
     p.stride = b->stride;
     p.len = b->len;
-    return family_kernel(pick_kernel(ctx, op, b, p));
+    p.addrs = nhc ? reinterpret_cast<const uint8_t*>(b) : nullptr;  // (only marks an NHC batch)
+    const Pick k = pick_kernel(PickCtx{variant, shape, desc_staged}, op, b, p);
+    out[0] = k.family;
+    out[1] = k.variant;
+    out[2] = k.shape;
+    return SMOL_OK;
+}
+
+const char* smol_csum_tool_kernel_for(const smol_csum_ctx_t* ctx, int op, const smol_csum_batch_t* b) {
+    int k[3];
+    if (!ctx || smol_csum_tool_pick(ctx->variant, ctx->shape, ctx->desc_staged, op, b, 0, k) != SMOL_OK) return "";
+    return family_kernel(k[0]);
+}
+
+int smol_csum_tool_variant_info(int variant, int out[4]) {
+    const Variant* r = find_variant(variant);
+    if (!r || !out) return SMOL_EINVAL;
+    out[0] = r->family;
+    out[1] = r->flags;
+    out[2] = r->built() ? 1 : 0;
+    out[3] = r->exp_only ? 1 : 0;
+    return SMOL_OK;
+}
+
+int smol_csum_tool_form(int variant, int op, int out[13]) {
+    if (!out || (op != MODE_EMIT && op != MODE_VERIFY)) return SMOL_EINVAL;
+    const bool emit = op == MODE_EMIT;
+    auto xw = [&](auto f) {
+        const int v[13] = {F_XWALK, f.NOSTORE, f.SEG, f.PERSIST, f.NTS,   f.HALF,  f.STAGE,
+                           f.HINT,  f.WPE,     f.WV,  f.STEPS,   f.ONLY_R, f.MAX_LEN == ~0u ? 0 : (int)f.MAX_LEN};
+        std::memcpy(out, v, sizeof v);
+    };
+    if (emit ? with_xwalk_form<true>(variant, xw) : with_xwalk_form<false>(variant, xw)) return SMOL_OK;
+    bool none = true;
+    auto dw = [&](auto f) {
+        const int v[13] = {F_DWALK, f.NOSTORE, f.GROUPS, f.SEGF, f.SEGPASS};
+        std::memcpy(out, v, sizeof v);
+        none = f.NONE;
+    };
+    const bool d = emit ? with_dwalk_form<true>(variant, dw) : with_dwalk_form<false>(variant, dw);
+    return d && !none ? SMOL_OK : SMOL_EINVAL;
 }
 
 uint32_t smol_csum_tool_last_launch(void) { return g_last_launch.load(std::memory_order_relaxed); }

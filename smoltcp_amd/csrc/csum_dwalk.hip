@@ -28,6 +28,7 @@
 // its own record, 8 lanes x U chunks per step.  The headers come from a 256-B LDS window
 // per record, loaded (two instructions for the 8 records) and parsed before the sums, whose masks
 // need each record's span end.
+#include "csum_variants.h"
 #include "csum_walk.h"
 
 namespace smolcsum {
@@ -48,18 +49,18 @@ constexpr uint32_t kStageMinBytes = 1024;  // STAGE: the wavefront's mean record
 // SEG (variant 61, emit): the 64-B segments that hold a record's fields go out whole from its LDS
 // window, the fields patched in, as the walk kernel's variant 39 does for fixed strides (§5 of
 // a whole segment is a plain write at the memory side, a 2-B store a read-modify-write).
-// SEGF bit 0: whole segments (variant 61); bit 1: the header windows loaded with the default cache
-// policy instead of non-temporal (62 = both, 63 = bit 1 alone); bit 2: the 2-B fields stored
-// non-temporal (experiments: 18 = 63 + bit 2, 20 = 60's emit + bit 2); bit 3: the window's 16
-// chunks summed from LDS, the stream starting at chunk 16 (41 = 63 + bit 3: the product's
-// descriptor-batch emit since late round 5); bit 4: staged (variant 94 = 61 + bits 1, 3 and 4, round 6):
-// a record whose fields the whole segments cover (bit 0's rule, all or nothing) writes nothing here and
-// stages one 8-B entry (its two field offsets and values) in p.stage for the segment pass
-// (seg_pass_desc_kernel); any other record stores its fields here as 2-B writes and stages ~0.
+// SEGF: bits of DwalkSegf (csum_variants.h).  DW_SEG: whole segments (variant 61); DW_WIN_CACHED: the
+// header windows loaded with the default cache policy instead of non-temporal (62 = both, 63 =
+// DW_WIN_CACHED alone); DW_FIELDS_NT: the 2-B fields stored non-temporal (experiments: 18 = 63 + it,
+// 20 = 60's emit + it); DW_WIN_SUM: the window's 16 chunks summed from LDS, the stream starting at
+// chunk 16 (41 = 63 + it: the descriptor-batch emit in place since late round 5); DW_STAGE: staged
+// (variant 94 = 62 + DW_WIN_SUM + it, round 6): a record whose fields the whole segments cover (DW_SEG's
+// rule, all or nothing) writes nothing here and stages one 8-B entry (its two field offsets and values)
+// in p.stage for the segment pass; any other record stores its fields here as 2-B writes and stages ~0.
 // tools/probe_wtax.hip: field writes that land while a read stream runs cost 65-90 ps each, the same
-// segments loaded again and written in a pass of their own ~40 ps.
+// segments loaded again and written in a pass of their own ~40 ps.  variants.def names each variant's bits.
 template <int MODE, bool NOSTORE, bool GROUPS = false, int SEGF = 0>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & 160) ? 8 : 1))) void dwalk_kernel(KParams p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & (DW_WAVES8 | DW_LITE_WAVES8)) ? 8 : 1))) void dwalk_kernel(KParams p) {
     using namespace dwalk;
     constexpr bool EMIT = MODE == MODE_EMIT;
     __shared__ u32x4 win[GPB][WIN_CH];
@@ -83,13 +84,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & 160
         const uint64_t off = (rw0 + (uint64_t)wl) * p.stride;
         d = u32x4{(uint32_t)off, (uint32_t)(off >> 32), (uint32_t)wl < cnt ? p.len : 0u, 0u};
     }
-    constexpr bool LITE = (SEGF & 64) != 0 && MODE == MODE_EMIT;
-    constexpr bool STAGE_ANY = (SEGF & 16) != 0 || LITE;
+    constexpr bool LITE = (SEGF & DW_LITE) != 0 && MODE == MODE_EMIT;
+    constexpr bool STAGE_ANY = (SEGF & DW_STAGE) != 0 || LITE;
     bool stage_wave = false;
-    // GAPS (bit 512, LITE, late round 6): a wavefront stages whatever its records' layout (gaps,
+    // GAPS (DW_GAPS, LITE, late round 6): a wavefront stages whatever its records' layout (gaps,
     // shuffled descriptors) when their mean length is >= kStageMinBytes; each record's segment may
     // start in the record before it only when that one (the batch's record r - 1) ends where it begins
-    constexpr bool GAPS = (SEGF & 512) != 0 && (SEGF & 64) != 0 && MODE == MODE_EMIT;
+    constexpr bool GAPS = (SEGF & DW_GAPS) != 0 && (SEGF & DW_LITE) != 0 && MODE == MODE_EMIT;
     uint64_t cmask = ~0ull;  // GAPS: lane j set when record j - 1 of the wavefront ends where j begins (>= 64 B)
     if constexpr (STAGE_ANY) {
         // from the descriptors in lanes 0 .. cnt - 1 (not the uniform arrays: they would stay live
@@ -116,7 +117,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & 160
     // LITE: the record before the wavefront's first one ends where it begins (the batch's record r - 1,
     // loaded with the descriptors), so that record 0's field segment may start in it (below)
     bool prev_contig = false;
-    if constexpr (LITE && (SEGF & 256) != 0) {
+    if constexpr (LITE && (SEGF & DW_FIRST) != 0) {
         if (rw0 > 0) {
             uint64_t pend;
             if (p.desc) {
@@ -148,12 +149,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & 160
     contig = contig && A[cnt - 1] + L[cnt - 1] - span_lo < (1ull << 31);
 
     // ---- the windows: instruction w, lane l: record 4 w + l / 16, chunk l % 16 ----
-    constexpr bool SEG = (SEGF & 1) != 0 && MODE == MODE_EMIT;
-    constexpr bool STAGE = (SEGF & 16) != 0 && SEG;
-    // LITE (bit 6, variant 96): staged like STAGE, but the decision (just before the finish) keeps
+    constexpr bool SEG = (SEGF & DW_SEG) != 0 && MODE == MODE_EMIT;
+    constexpr bool STAGE = (SEGF & DW_STAGE) != 0 && SEG;
+    // LITE (DW_LITE, variant 96): staged like STAGE, but the decision (just before the finish) keeps
     // only its outcome and the field values go to the entry from finish_gates' registers (no window
     // patch, no whole-segment addresses): variant 41's finish otherwise
-    constexpr bool WNT = (SEGF & 2) == 0;
+    constexpr bool WNT = (SEGF & DW_WIN_CACHED) == 0;
     const bool mine = (uint32_t)gw < cnt;
     const uint64_t r = rw0 + (uint64_t)gw;
     const uint64_t a0 = (uint64_t)p.buf + ((uint64_t)(uint32_t)__shfl((int)d.x, gw, 64) |
@@ -308,7 +309,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & 160
         const uint64_t base = a0 & ~127ull;
         const uint32_t nch = (uint32_t)((int)hd + s1 + 15) >> 4;  // chunks up to the span's end
         uint32_t cstart = 0;
-        if constexpr ((SEGF & 8) != 0) {  // the window's chunks from LDS, the stream from chunk 16
+        if constexpr ((SEGF & DW_WIN_SUM) != 0) {  // the window's chunks from LDS, the stream from chunk 16
 #pragma unroll
             for (int h = 0; h < WIN_CH / G; ++h) {
                 const uint32_t c = (uint32_t)(G * h + lane);
@@ -371,7 +372,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & 160
     }
     // ---- finish: the walk kernel's gates ----
     if constexpr (LITE) {
-        if (mine) finish_gates<G, MODE, false, decltype(rd), 0, false, NOSTORE, (SEGF & 1024) != 0, true>(p, g, a1, rd, winb, hd, a0, r, lane,
+        if (mine) finish_gates<G, MODE, false, decltype(rd), 0, false, NOSTORE, (SEGF & DW_ENTRIES_NT) != 0, true>(p, g, a1, rd, winb, hd, a0, r, lane,
                                                                                             nullptr, ~0ull, ~0ull,
                                                                                             !stage_wave ? 0 : lite_staged ? 1 : 2);
         if (wl == 0) p.stage_flags[rw0 / R] = stage_wave ? 1u : 0u;
@@ -398,7 +399,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & 160
             if (wsB != ~0ull && lane < 8) seg_store(wsB + 8u * (uint32_t)lane);
         }
     } else {
-        if (mine) finish_gates<G, MODE, false, decltype(rd), 0, false, NOSTORE, (SEGF & 4) != 0>(p, g, a1, rd, winb, hd, a0, r, lane);
+        if (mine) finish_gates<G, MODE, false, decltype(rd), 0, false, NOSTORE, (SEGF & DW_FIELDS_NT) != 0>(p, g, a1, rd, winb, hd, a0, r, lane);
     }
 }
 
@@ -503,68 +504,38 @@ hipError_t launch_seg_pass(const KParams& p, hipStream_t s, int form) {
     return hipGetLastError();
 }
 
-hipError_t launch_dwalk(int mode, int variant, const KParams& p, hipStream_t s) {
-#ifndef SMOL_EXP
-    // the product's forms: 63 (verify / emit), 41 (emit), 60 (verify)
-    if (!(variant == 63 && (mode == MODE_VERIFY || mode == MODE_EMIT)) && !(variant == 60 && mode == MODE_VERIFY) &&
-        !(variant == 41 && mode == MODE_EMIT) && !(variant == 94 && mode == MODE_EMIT) && !(variant == 95 && mode == MODE_EMIT) &&
-        !(variant == 96 && mode == MODE_EMIT) && !(variant == 97 && mode == MODE_EMIT))
+// One launch (and, for a staged form, its segment pass) of the form the registry gives (variant, mode).
+template <int MODE, class F>
+static hipError_t launch_dwalk_form(const KParams& p, hipStream_t s) {
+    if constexpr (F::NONE) {
         return hipErrorInvalidValue;
-#endif
-    if ((variant == 94 || variant == 95 || variant == 96 || variant == 97 || (variant >= 103 && variant <= 105) || variant == 109) &&
-        mode == MODE_EMIT) {  // staged: the staging launch, then the segment pass
-        if (!p.stage || !p.stage_flags || p.n > kStageChunk) return hipErrorInvalidValue;
-        note_launch(KERN_DWALK, (uint32_t)variant, dwalk::G, dwalk::U);
+    } else {
         const uint32_t b = grid_blocks((p.n + dwalk::GPB - 1) / dwalk::GPB, kMaxGridBlocks);
-        if (variant == 96)  // held to 8 wavefronts per SIMD (12 B of spills per lane; 97: 7, none)
-            hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 10 | 64 | 128>), dim3(b), dim3(256), 0, s, p);
-        else if (variant == 97 || variant == 105)  // (bit 256, late round 6: the wavefront's first record may stage too; 105: the first segment-pass form)
-            hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 10 | 64 | 256>), dim3(b), dim3(256), 0, s, p);
-#ifdef SMOL_EXP
-        else if (variant == 109)  // 97 + bit 1024 (experiments build): entries (and 2-B fields) stored write-through / nt
-            hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 10 | 64 | 256 | 1024>), dim3(b), dim3(256), 0, s, p);
-        else if (variant == 104)  // 97 + bit 512 (experiments build): staging over gapped / shuffled layouts
-            hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 10 | 64 | 256 | 512>), dim3(b), dim3(256), 0, s, p);
-        else if (variant == 103)  // 97 before bit 256 (experiments build)
-            hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 10 | 64>), dim3(b), dim3(256), 0, s, p);
-#endif
-        else if (variant == 95)  // (experiments: held to 8 wavefronts per SIMD, 64 B of spills per lane)
-            hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 27 | 32>), dim3(b), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 27>), dim3(b), dim3(256), 0, s, p);
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        return launch_seg_pass(p, s, variant == 105 ? 1 : 0);
+        hipLaunchKernelGGL((dwalk_kernel<MODE, F::NOSTORE, F::GROUPS, F::SEGF>), dim3(b), dim3(256), 0, s, p);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess || F::SEGPASS < 0) return e;
+        return launch_seg_pass(p, s, F::SEGPASS);
     }
-    const uint64_t per = (uint64_t)dwalk::GPB;
+}
+
+hipError_t launch_dwalk(int mode, int variant, const KParams& p, hipStream_t s) {
+    if (mode != MODE_EMIT && mode != MODE_VERIFY) return hipErrorInvalidValue;
+    // staged: one staging launch and its segment pass over at most kStageChunk records (run() chunks)
+    const bool staged = mode == MODE_EMIT && variant_is(variant, V_STAGED);
+    if (staged && (!p.stage || !p.stage_flags || p.n > kStageChunk)) return hipErrorInvalidValue;
     note_launch(KERN_DWALK, (uint32_t)variant, dwalk::G, dwalk::U);
-    const uint64_t span = kMaxGridBlocks * per;
+    const uint64_t span = kMaxGridBlocks * (uint64_t)dwalk::GPB;
     for (uint64_t i0 = 0; i0 < p.n; i0 += span) {
         KParams q = p;
         q.n = p.n - i0 < span ? p.n - i0 : span;
         if (p.desc) q.desc = p.desc + i0;
         else q.buf = p.buf + i0 * p.stride;
         if (p.status) q.status = p.status + i0;
-        const uint32_t b = grid_blocks((q.n + per - 1) / per, kMaxGridBlocks);
-        if (variant == 63 && mode == MODE_VERIFY)
-            hipLaunchKernelGGL((dwalk_kernel<MODE_VERIFY, false, true, 2>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 63)
-            hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 2>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 41)
-            hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 10>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 60 && mode == MODE_VERIFY)
-            hipLaunchKernelGGL((dwalk_kernel<MODE_VERIFY, false, true>), dim3(b), dim3(256), 0, s, q);
-#ifdef SMOL_EXP
-        else if (variant == 60) hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 18) hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 6>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 20) hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 4>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 61) hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 1>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 62) hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, 3>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 64 + 61) hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, true, true, 1>), dim3(b), dim3(256), 0, s, q);
-        else if (mode == MODE_VERIFY) hipLaunchKernelGGL((dwalk_kernel<MODE_VERIFY, false>), dim3(b), dim3(256), 0, s, q);
-        else if (variant >= 64) hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, true>), dim3(b), dim3(256), 0, s, q);
-        else hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false>), dim3(b), dim3(256), 0, s, q);
-#endif
-        const hipError_t e = hipGetLastError();
+        hipError_t e = hipSuccess;
+        const bool known =
+            mode == MODE_EMIT ? with_dwalk_form<true>(variant, [&](auto f) { e = launch_dwalk_form<MODE_EMIT, decltype(f)>(q, s); })
+                              : with_dwalk_form<false>(variant, [&](auto f) { e = launch_dwalk_form<MODE_VERIFY, decltype(f)>(q, s); });
+        if (!known) return hipErrorInvalidValue;  // not a descriptor-walk variant of this library
         if (e != hipSuccess) return e;
     }
     return hipSuccess;

@@ -119,25 +119,17 @@ hipError_t launch_walk_nhc(int shape, int var, const KParams& p, uint32_t max_bl
 hipError_t launch_tile(int mode, int shape, int var, int tile_records, const KParams& p, uint32_t max_blocks,
                        hipStream_t s);
 
-// Stripe kernel (csum_tile.hip, variant 42): fixed-stride packed records of 1024-1520 bytes.
-bool stripe_fits(const KParams& p);
+// The other families (which batches each serves: csum_dispatch.h; which variant runs which form of
+// xwalk_kernel / dwalk_kernel: variants.def).  Stripe kernel: csum_tile.hip; transposed walk:
+// csum_xwalk.hip; copy-emit on its layout: csum_xcopy.hip; descriptor-batch walks: csum_dwalk.hip.
 hipError_t launch_stripe(int mode, const KParams& p, hipStream_t s);
-// Transposed walk (csum_xwalk.hip, variants 44 / 47 = whole field segments): fixed-stride packed
-// records of 1024-16257 bytes.
-bool xwalk_fits(const KParams& p);
-// Copy-emit on the transposed walk's layout (csum_xcopy.hip, variants 49 / 50 = persistent grid,
-// experiments build): fixed-stride records of 1024-1921 bytes.
-bool xcopy_fits(const KParams& p);
-// Descriptor-batch walks (csum_dwalk.hip): variant 60 = verify default; 56 / 60 emit: experiments.
 hipError_t launch_dwalk(int mode, int variant, const KParams& p, hipStream_t s);
 hipError_t launch_xcopy(int variant, const KParams& p, hipStream_t s);
 hipError_t launch_xwalk(int mode, int variant, const KParams& p, hipStream_t s);
-// Staged emit (variants 80 / 81): the transposed walk writes each record's field entry to p.stage, then
-// the segment pass writes the field segments whole (csum_xwalk.hip).  Records per launch pair:
+// Staged emit (the registry's V_STAGED variants): the staging launch writes each record's field entry to
+// p.stage, then the segment pass (csum_dwalk.hip; form 0 seg_pass4_kernel, 1 the first form, experiments
+// build) writes the field segments whole.  Records per launch pair:
 constexpr uint64_t kStageChunk = 1ull << 21;
-inline bool staged_variant(int v) { return v == 80 || v == 81; }
-inline bool staged_desc_variant(int v) { return (v >= 94 && v <= 97) || (v >= 103 && v <= 105) || v == 109; }  // csum_dwalk.hip
-// The segment pass of the staged emit (csum_dwalk.hip seg_pass4_kernel), after the staging launch.
 hipError_t launch_seg_pass(const KParams& p, hipStream_t s, int form = 0);
 
 // Synthetic batches and fault injection (tools; include/smolcsum_tools.h).

@@ -1,5 +1,5 @@
 // Tile kernel: batched emit / verify for MI355X (gfx950).  The library's default only for emit over
-// descriptor batches (C3; csum_api.cpp auto_variant); every other call runs the walk kernel.
+// descriptor batches (C3; csum_dispatch.h auto_variant); every other call runs the walk kernel.
 //
 // A wavefront owns a TILE of 32 or 64 consecutive records and works on it in three phases:
 //
@@ -27,7 +27,7 @@
 #include <stdint.h>
 
 #include "csum_device.h"
-#include "csum_launch.h"
+#include "csum_dispatch.h"
 
 namespace smolcsum {
 
@@ -404,7 +404,7 @@ __global__ __launch_bounds__(256) void csum_tile_kernel(KParams p) {
 // of a record's first chunk that follow its start (the chunk is attributed to the previous record)
 // are moved back in phase C from the record's window: + its own, - its successor's (a lane shuffle).
 // Bytes before the first record and past the last are masked.  Phase C is the tile kernel's.
-constexpr int STRIPE_T = 8;
+constexpr int STRIPE_T = kStripeRecords;  // (csum_dispatch.h stripe_fits)
 
 template <int MODE, int NU>
 __global__ __launch_bounds__(256) void csum_stripe_kernel(KParams p) {
@@ -549,16 +549,6 @@ static hipError_t launch_mode(int shape, int var, const KParams& p, uint32_t max
 }
 
 }  // namespace tile
-
-// The stripe kernel serves fixed-stride batches of packed records (stride == len) of 1024 .. 1520
-// bytes over a natural grid; false: not this batch.
-bool stripe_fits(const KParams& p) {
-#ifdef SMOL_EXP
-    return p.desc == nullptr && p.len == p.stride && p.len >= 1024 && p.len <= (12 * 1024 - 127) / tile::STRIPE_T;
-#else
-    return false;
-#endif
-}
 
 hipError_t launch_stripe(int mode, const KParams& p, hipStream_t s) {
 #ifdef SMOL_EXP

@@ -1,0 +1,224 @@
+// Reader of variants.def: the variant table and its lookups, the named forms of xwalk_kernel and
+// dwalk_kernel, and the switches from (variant, mode) to a form.  Host-only (no HIP): csum_dispatch.h,
+// the launchers and the tooling entry points all read variants through this file.
+#pragma once
+
+#include <stdint.h>
+
+namespace smolcsum {
+
+enum Family { F_WALK, F_TILE, F_XWALK, F_DWALK, F_STRIPE, F_COPY, F_XCOPY };
+enum VariantFlags { V_COPY_ONLY = 1, V_WALK_COPY = 2, V_LINE = 4, V_G16U4 = 8, V_STAGED = 16, V_NOSTORE = 32, V_NHC_LINE = 64 };
+
+// ---- xwalk_kernel's forms (csum_xwalk.hip explains each constant) -----------------------------------
+enum XwalkNts {
+    NTS_PLAIN = 0,
+    NTS_NT = 1,                   // the segments stored non-temporal, always (57)
+    NTS_NT_IF_IPV4 = 2,           // ... on a wavefront that holds an IPv4 record (58)
+    NTS_HEAD_KIB_CACHED = 4,      // each record's first load instruction (its first KiB) with the default cache policy (45)
+    NTS_HEAD_KIB_CACHED_NT = 5,   // 45 with the segments stored non-temporal (15)
+    NTS_ALL_CACHED = 8,           // every load with the default cache policy (43)
+    NTS_HEAD_LINES_CACHED = 16,   // only the record's two header lines (lanes 0-15 of its first instruction) cached (46)
+    NTS_STAGE_FIELDS_CACHED = 32, // staged: the lanes that hold the segments of record offsets [10, 28) cached (80)
+    NTS_WT_SC0 = 64,              // the segments stored sc0 sc1 nt (100)
+    NTS_WT = 65,                  // the segments stored sc1 nt, write-through and non-temporal (101)
+    NTS_STATUS_NT = 128,          // verify: the status bytes stored non-temporal (108)
+};
+// Lanes of a record's first load instruction that load with the default cache policy (the rest nt).
+enum XwalkHint {
+    HINT_NONE = 0,
+    HINT_FIELD_SEGS = 1,     // the segments of record offsets [10, 28) (an IPv4 record's fields)
+    HINT_FIRST_64 = 2,       // those of [0, 64)
+    HINT_WINDOW = 3,         // the whole 256-B window
+    HINT_SEG_OF_10 = 4,      // the segment of offset 10 only
+    HINT_CHUNK_OF_10 = 5,    // the 16-B chunk of offset 10 only
+    HINT_FIRST_SEG = 6,      // the segment of the record's first byte
+    HINT_LINE_HEAD = 7,      // the line's first segment (lanes 0-3)
+    HINT_SPLIT_ONLY = 8,     // instruction 0 split in two (lanes 0-3 / the rest), both non-temporal
+    HINT_LINE_HEAD_2ND = 9,  // lanes 0-3 of instruction 1 with the default policy
+    HINT_LINE_HEAD_ALL = 10, // lanes 0-3 of every instruction
+};
+
+// The defaults: 2-B field stores (emit), nothing hinted; also the form run where a form's ONLY_R /
+// MAX_LEN does not hold.
+struct XPlain {
+    static constexpr bool NOSTORE = false, SEG = false, PERSIST = false, HALF = false, STAGE = false;
+    static constexpr int NTS = NTS_PLAIN, HINT = HINT_NONE;
+    static constexpr int WPE = 0;    // wavefronts per SIMD the kernel is held to (0: the compiler's)
+    static constexpr int WV = 4;     // wavefronts per workgroup (8: 512 threads, half the grid)
+    static constexpr int STEPS = 1;  // tiles per workgroup (2: half the grid)
+    static constexpr int ONLY_R = 0;               // the form exists at this many records per wavefront only
+    static constexpr uint32_t MAX_LEN = ~0u;       // ... and up to this record length
+};
+template <int N> struct XNts : XPlain { static constexpr int NTS = N; };
+template <int H> struct XHint : XPlain { static constexpr int HINT = H; };
+template <int W> struct XHint7Wpe : XHint<HINT_LINE_HEAD> { static constexpr int WPE = W; };
+struct XNoStoreHint : XHint<HINT_LINE_HEAD> { static constexpr bool NOSTORE = true; };
+struct XStatusNt : XHint<HINT_LINE_HEAD> { static constexpr int NTS = NTS_STATUS_NT; };
+struct XWide : XHint<HINT_LINE_HEAD> { static constexpr int WV = 8, ONLY_R = 8; };
+struct XTwoTiles : XHint<HINT_LINE_HEAD> { static constexpr int STEPS = 2; };
+struct XHalf : XPlain { static constexpr bool HALF = true; static constexpr int ONLY_R = 8; static constexpr uint32_t MAX_LEN = 1409; };
+struct XPersist : XPlain { static constexpr bool PERSIST = true; };
+struct XSeg : XPlain { static constexpr bool SEG = true; };
+template <int N> struct XSegNts : XSeg { static constexpr int NTS = N; };
+template <int H> struct XSegHint : XSeg { static constexpr int HINT = H; };
+template <int H> struct XSegNtHint : XSegNts<NTS_NT> { static constexpr int HINT = H; };
+template <int H> struct XSegWtHint : XSegNts<NTS_WT> { static constexpr int HINT = H; };
+template <int W> struct XSegNtWpe : XSegNts<NTS_NT> { static constexpr int WPE = W; };
+struct XSegWtTwoTiles : XSegNts<NTS_WT> { static constexpr int STEPS = 2; };
+struct XSegHalf : XSeg { static constexpr bool HALF = true; static constexpr int ONLY_R = 8; static constexpr uint32_t MAX_LEN = 1409; };
+struct XSegPersist : XSeg { static constexpr bool PERSIST = true; };
+struct XSegNoStore : XSeg { static constexpr bool NOSTORE = true; };
+struct XStage : XSeg { static constexpr bool STAGE = true; };
+struct XStageCached : XStage { static constexpr int NTS = NTS_STAGE_FIELDS_CACHED; };
+
+// ---- dwalk_kernel's forms (csum_dwalk.hip) ----------------------------------------------------------
+enum DwalkSegf {
+    DW_SEG = 1,             // whole 64-B field segments from the LDS window (61)
+    DW_WIN_CACHED = 2,      // the header windows loaded with the default cache policy (63)
+    DW_FIELDS_NT = 4,       // the 2-B fields stored non-temporal (18, 20)
+    DW_WIN_SUM = 8,         // the window's 16 chunks summed from LDS, the stream from chunk 16 (41)
+    DW_STAGE = 16,          // staged, the first form: with DW_SEG, entries from the patched window (94)
+    DW_WAVES8 = 32,         // held to 8 wavefronts per SIMD (95)
+    DW_LITE = 64,           // staged from the finish's registers: no window patch, no segment addresses (96, 97)
+    DW_LITE_WAVES8 = 128,   // held to 8 wavefronts per SIMD (96)
+    DW_FIRST = 256,         // the wavefront's first record may stage too (97)
+    DW_GAPS = 512,          // staging over gapped / shuffled layouts (104)
+    DW_ENTRIES_NT = 1024,   // entries and 2-B fields stored write-through non-temporal (109)
+};
+struct DNone {  // the variant has no form of this mode (in this library)
+    static constexpr bool NONE = true, NOSTORE = false, GROUPS = false;
+    static constexpr int SEGF = 0;
+    static constexpr int SEGPASS = -1;  // the segment pass after the launch: -1 none, 0 seg_pass4_kernel, 1 the first form
+};
+struct DSpan : DNone { static constexpr bool NONE = false; };
+struct DSpanNoStore : DSpan { static constexpr bool NOSTORE = true; };
+struct DGroups : DSpan { static constexpr bool GROUPS = true; };
+template <int S> struct DG : DGroups { static constexpr int SEGF = S; };
+struct DSegNoStore : DG<DW_SEG> { static constexpr bool NOSTORE = true; };
+template <int S> struct DStaged : DG<S> { static constexpr int SEGPASS = 0; };
+using DLiteFirst = DStaged<DW_WIN_CACHED | DW_WIN_SUM | DW_LITE | DW_FIRST>;
+struct DLiteFirstPass8B : DLiteFirst { static constexpr int SEGPASS = 1; };
+
+#ifdef SMOL_EXP
+#define EXP_ONLY(form) form
+constexpr bool kExpBuild = true;
+#else
+#define EXP_ONLY(form) DNone
+constexpr bool kExpBuild = false;
+#endif
+
+// ---- the table --------------------------------------------------------------------------------------
+struct Variant {
+    int num;
+    int family;
+    bool exp_only;     // built in the experiments library only
+    int flags;         // VariantFlags
+    int field_twin;    // SMOL_BATCH_FIELD_STORES (emit)
+    int verify_twin;
+    int tile_loads;    // F_TILE: the tile kernel's load form
+    bool emit, verify; // F_XWALK / F_DWALK: a form of that mode exists in this library
+    const char* desc;
+    bool is(int f) const { return (flags & f) != 0; }
+    bool built() const { return !exp_only || kExpBuild; }
+};
+
+#define SELF (-1)
+#define V_BUILD_P false
+#define V_BUILD_X true
+inline constexpr Variant kVariants[] = {
+#define WALK(n, b, fl, ft, d) {n, F_WALK, V_BUILD_##b, fl, ft, SELF, 0, true, true, d},
+#define TILE(n, b, loads, d) {n, F_TILE, V_BUILD_##b, 0, SELF, SELF, loads, true, true, d},
+#define STRIPE(n, b, d) {n, F_STRIPE, V_BUILD_##b, 0, SELF, SELF, 0, true, true, d},
+#define COPY(n, b, d) {n, F_COPY, V_BUILD_##b, V_COPY_ONLY, SELF, SELF, 0, false, false, d},
+#define XCOPY(n, b, d) {n, F_XCOPY, V_BUILD_##b, V_COPY_ONLY, SELF, SELF, 0, false, false, d},
+#define XWALK(n, b, fl, ft, ef, vf, d) {n, F_XWALK, V_BUILD_##b, fl, ft, SELF, 0, true, true, d},
+#define DWALK(n, b, fl, ft, vt, ef, vf, d) {n, F_DWALK, V_BUILD_##b, fl, ft, vt, 0, !ef::NONE, !vf::NONE, d},
+#include "variants.def"
+#undef WALK
+#undef TILE
+#undef STRIPE
+#undef COPY
+#undef XCOPY
+#undef XWALK
+#undef DWALK
+};
+
+// The row of a number (nullptr: none; -1, the automatic choice, has none).
+inline const Variant* find_variant(int v) {
+    for (const Variant& r : kVariants)
+        if (r.num == v) return &r;
+    return nullptr;
+}
+inline bool variant_built(int v) {
+    const Variant* r = find_variant(v);
+    return v == -1 || (r && r->built());
+}
+inline bool variant_is(int v, int flag) {
+    const Variant* r = find_variant(v);
+    return r && r->is(flag);
+}
+inline int field_store_variant(int v) {
+    const Variant* r = find_variant(v);
+    return r && r->field_twin != SELF ? r->field_twin : v;
+}
+inline int verify_variant(int v) {
+    const Variant* r = find_variant(v);
+    return r && r->verify_twin != SELF ? r->verify_twin : v;
+}
+
+// (variant, mode) -> form: calls fn(Form{}) for the row's emit (EMIT) or verify form, over the rows built
+// in this library; false: no such row.  The launchers instantiate kernels through these switches and
+// smol_csum_tool_form reads the same ones.
+#define V_FORM_P(n, ef, vf)            \
+    case n:                            \
+        if constexpr (EMIT) fn(ef{});  \
+        else fn(vf{});                 \
+        return true;
+#ifdef SMOL_EXP
+#define V_FORM_X(n, ef, vf) V_FORM_P(n, ef, vf)
+#else
+#define V_FORM_X(n, ef, vf)
+#endif
+#define WALK(n, b, fl, ft, d)
+#define TILE(n, b, loads, d)
+#define STRIPE(n, b, d)
+#define COPY(n, b, d)
+#define XCOPY(n, b, d)
+
+template <bool EMIT, class Fn>
+inline bool with_xwalk_form(int variant, Fn&& fn) {
+    switch (variant) {
+#define XWALK(n, b, fl, ft, ef, vf, d) V_FORM_##b(n, ef, vf)
+#define DWALK(n, b, fl, ft, vt, ef, vf, d)
+#include "variants.def"
+#undef XWALK
+#undef DWALK
+        default: return false;
+    }
+}
+
+template <bool EMIT, class Fn>
+inline bool with_dwalk_form(int variant, Fn&& fn) {
+    switch (variant) {
+#define XWALK(n, b, fl, ft, ef, vf, d)
+#define DWALK(n, b, fl, ft, vt, ef, vf, d) V_FORM_##b(n, ef, vf)
+#include "variants.def"
+#undef XWALK
+#undef DWALK
+        default: return false;
+    }
+}
+#undef WALK
+#undef TILE
+#undef STRIPE
+#undef COPY
+#undef XCOPY
+#undef V_FORM_P
+#undef V_FORM_X
+#undef V_BUILD_P
+#undef V_BUILD_X
+#undef EXP_ONLY
+#undef SELF
+
+}  // namespace smolcsum

@@ -41,6 +41,7 @@
 
 #include "csum_device.h"
 #include "csum_launch.h"
+#include "csum_variants.h"
 
 namespace smolcsum {
 
@@ -62,7 +63,8 @@ namespace smolcsum {
 // 31 = 5 with the geometry in LDS and no shared_from; 32 = 29 with both; 33 = 29 with the geometry
 // in LDS; 34 = 29 without shared_from; 35 = 5 without shared_from; 36 = 5 with the geometry in LDS.
 // VAR | 64 (experiments): the same kernel with every global store of emit compiled out (the values
-// computed and kept live, nothing written; wrong bytes, timing only).
+// computed and kept live, nothing written; wrong bytes, timing only).  Round 6 reused most numbers from
+// 64 up for other kernels: of these only 64 + 5 is still the walk kernel's (variants.def has every row).
 template <int VAR_>
 struct VarT {
     static constexpr int VAR = VAR_ & 63;
@@ -1320,7 +1322,7 @@ hipError_t launch_seg_shape(int shape, const KParams& p, uint32_t max_blocks, hi
 }
 
 #ifdef SMOL_EXP
-// Experiment variants of fixed-stride emit (31-38, and | 64 without stores): the two fixed-stride
+// Experiment variants of fixed-stride emit (31-38, and 64 + 5 without stores): the two fixed-stride
 // shapes only (other shapes map to the one with the same group size).
 template <int VAR>
 hipError_t launch_emit_exp(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s) {
@@ -1344,17 +1346,7 @@ hipError_t launch_walk_exp(int shape, int var, const KParams& p, uint32_t max_bl
             case 40: return launch_emit_exp<40>(shape, p, max_blocks, s);
             case 12: return launch_emit_exp<12>(shape, p, max_blocks, s);
             case 14: return launch_emit_exp<14>(shape, p, max_blocks, s);
-            case 64 + 39: return launch_emit_exp<64 + 39>(shape, p, max_blocks, s);
-            case 64 + 5: return launch_emit_exp<64 + 5>(shape, p, max_blocks, s);
-            case 64 + 29: return launch_emit_exp<64 + 29>(shape, p, max_blocks, s);
-            case 64 + 31: return launch_emit_exp<64 + 31>(shape, p, max_blocks, s);
-            case 64 + 32: return launch_emit_exp<64 + 32>(shape, p, max_blocks, s);
-            case 64 + 33: return launch_emit_exp<64 + 33>(shape, p, max_blocks, s);
-            case 64 + 34: return launch_emit_exp<64 + 34>(shape, p, max_blocks, s);
-            case 64 + 35: return launch_emit_exp<64 + 35>(shape, p, max_blocks, s);
-            case 64 + 36: return launch_emit_exp<64 + 36>(shape, p, max_blocks, s);
-            case 64 + 37: return launch_emit_exp<64 + 37>(shape, p, max_blocks, s);
-            case 64 + 38: return launch_emit_exp<64 + 38>(shape, p, max_blocks, s);
+            case 64 + 5: return launch_emit_exp<64 + 5>(shape, p, max_blocks, s);  // (the one | 64 number the walk kernel still owns)
             default: break;
         }
     }
@@ -1399,7 +1391,7 @@ hipError_t launch_walk_exp(int shape, int var, const KParams& p, uint32_t max_bl
 }
 #endif
 
-// The product variants (csum_api.cpp variant_built): 5 (line grid, nt loads, register prefetch),
+// The product variants (variants.def, build P): 5 (line grid, nt loads, register prefetch),
 // 13 (5 without the prefetch) and, for fixed-stride emit, 39 (5 with whole field segments: 29's
 // LDS-published decision on wavefronts with an IPv4 record, one ballot on the others).  Other
 // variants: the experiments build.
@@ -1426,8 +1418,8 @@ hipError_t launch_walk(int shape, int var, const KParams& p, uint32_t max_blocks
 template <int MODE, bool IMPLICIT>
 hipError_t launch_walk_nhc(int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s) {
     const int g = (shape == CFG_G8U6 || shape == CFG_G8U7) ? shape : CFG_G16U3;
-    // the line-grid variants (the descriptor-verify default 13 included) run variant 5 here
-    if (var == 5 || var == 6 || var == 9 || var == 10 || var == 13 || var == 19 || (var >= 23 && var <= 29)) {
+    // the registry's V_NHC_LINE variants (the descriptor-verify default 13 included) run variant 5 here
+    if (variant_is(var, V_NHC_LINE)) {
         if (g == CFG_G8U6) return launch_one<8, 6, MODE, IMPLICIT, 5, true>(p, max_blocks, s);
         if (g == CFG_G8U7) return launch_one<8, 7, MODE, IMPLICIT, 5, true>(p, max_blocks, s);
         return launch_one<16, 3, MODE, IMPLICIT, 5, true>(p, max_blocks, s);

@@ -410,14 +410,6 @@ __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
 
 #endif  // SMOL_EXP
 
-bool xcopy_fits(const KParams& p) {
-#ifdef SMOL_EXP
-    return p.desc == nullptr && p.stride >= p.len && p.len >= 1024 && p.len <= 1921 && p.stride <= (1ull << 26);
-#else
-    return false;
-#endif
-}
-
 hipError_t launch_xcopy(int variant, const KParams& p, hipStream_t s) {
 #ifdef SMOL_EXP
     const uint64_t per = (uint64_t)xcopy::GPB;

@@ -27,8 +27,9 @@
 // 64-bit-address load from the dummy line for out-of-range chunks, a persistent grid (one wavefront
 // steps over the batch 8 records at a time, with or without the next step's loads issued ahead:
 // PERSIST, variant 48) and 5 wavefronts per SIMD (96 VGPRs), were all slower.  The library uses it
-// where it beats the walk kernel (csum_api.cpp xwalk_auto): verify of packed records from 1473 B
+// where it beats the walk kernel (csum_dispatch.h xwalk_auto): verify of packed records from 1473 B
 // (not multiples of 128 B below 1666 B), verify of gapped records and emit from 1666 B, up to 8065 B.
+#include "csum_dispatch.h"
 #include "csum_walk.h"
 
 namespace smolcsum {
@@ -67,43 +68,35 @@ __device__ __forceinline__ uint32_t reduce_scatter(const uint32_t* acc, int wl) 
 
 }  // namespace xwalk
 
+// F: the form, one of csum_variants.h's named structs (XPlain and what differs from it); variants.def
+// says which variant runs which form in emit and in verify.  Its constants:
 // SEG (variant 47; emit): the 64-B segments that hold a record's fields go out whole from its LDS
 // window, the fields patched in (csum_walk.h variant 38's decision, the wavefront's groups all on
 // their one record): a whole segment costs HBM a plain write where a 2-B store costs a
-// read-modify-write.  NOSTORE (variant 64 + v): emit computes every field value and stores none.
+// read-modify-write.  NOSTORE (experiments, timing only): every value computed, none stored.
 // PERSIST (variant 48, experiments build): a grid of the resident workgroups whose wavefronts step
 // over the batch, issuing the next step's loads as soon as this step's sums are taken (before its
 // finish and stores), so that no wavefront ends while its stores drain.
-// NTS: the segments stored non-temporal, always (variant 57, the product's emit of packed
-// 1400-1580-B records, csum_api.cpp xwalk_auto) or on a wavefront that holds an IPv4 record (58,
-// experiments build).  NTS = 4 (variant 45, experiments build): each record's first load
-// instruction (its first KiB, header lines included) with the default cache policy instead of
-// non-temporal, so that the field stores hit lines the L2 holds (the descriptor walk's variant 63
-// finding).  NTS = 8 (variant 43,
-// experiments build): every load with the default cache policy; NTS = 16 (variant 46, experiments
-// build): only the record's two header lines (lanes 0-15 of its first instruction) cached; NTS = 5
-// (variant 15, experiments build): 45 with the segments stored non-temporal.
+// NTS (XwalkNts): the cache policy of the segment stores and of some loads.  Cached header loads (45, 43,
+// 46, 15) follow the descriptor walk's variant 63 finding: the field stores hit lines the L2 holds.
+// NTS_WT (variant 101, the product's emit where the dispatch table says 't', since late round 6) is the
+// staged emit's segment-pass policy inside the stream, as a vector store written as the instruction.
+// HINT (XwalkHint): lanes of a record's first load instruction that load with the default policy.
 // HALF (variant 59, experiments build; R = 8, records of at most 1409 B, whose line-grid span fits
 // 96 chunks): a record's second KiB is half an instruction, two records per instruction, so a
 // wavefront issues 12 loads instead of 16.
-// NTS = 65 (variant 101, the product's emit where the dispatch table says 'n', since late round 6): the
-// segments stored with sc1 nt, write-through and non-temporal (the staged emit's segment-pass policy,
-// here inside the stream), as a vector store written as the instruction; NTS = 64 (variant 100,
-// experiments build): sc0 sc1 nt.
 // STAGE (variants 80 / 81, round 6; emit): the field segments are not written here.  A record whose
 // fields the whole segments cover (47's rule, all or nothing) stages one 8-B entry (its two field
 // offsets and values, csum_walk.h stage_entry) in p.stage, and the segment pass (csum_dwalk.hip
-// seg_pass4_kernel) writes the segments after this launch; any other
-// record writes its fields here as 2-B stores and stages nothing.  NTS = 32 (variant 80): the
-// lanes of a record's first instruction that hold the segments of record offsets [10, 28) (an IPv4
-// record's two fields) load with the default cache policy, so that the segment pass finds those lines
-// on chip; 81: every load non-temporal.  Why (tools/probe_wtax.hip): field
-// writes that land while a read stream runs cost 65-77 ps each, the same writes in a pass of their own
-// ~20 ps.
-template <int MODE, int R, bool NOSTORE, bool SEG, bool PERSIST = false, int NTS = 0, bool HALF = false,
-          bool STAGE = false, int HINT = 0, int WPE = 0, int WV = xwalk::WAVES, int STEPS = 1>
-__global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WPE > 0 ? WPE : 1))) void xwalk_kernel(KParams p) {
+// seg_pass4_kernel) writes the segments after this launch; any other record writes its fields here as
+// 2-B stores and stages nothing.  Why (tools/probe_wtax.hip): field writes that
+// land while a read stream runs cost 65-77 ps each, the same writes in a pass of their own ~20 ps.
+// WPE, WV, STEPS: wavefronts per SIMD the kernel is held to, per workgroup, tiles per workgroup.
+template <int MODE, int R, class F>
+__global__ __launch_bounds__(64 * F::WV) __attribute__((amdgpu_waves_per_eu(F::WPE > 0 ? F::WPE : 1))) void xwalk_kernel(KParams p) {
     using namespace xwalk;
+    constexpr bool NOSTORE = F::NOSTORE, SEG = F::SEG, PERSIST = F::PERSIST, HALF = F::HALF, STAGE = F::STAGE;
+    constexpr int NTS = F::NTS, HINT = F::HINT, WV = F::WV, STEPS = F::STEPS;
     constexpr bool EMIT = MODE == MODE_EMIT;
     constexpr int G = 64 / R;    // lanes per record
     constexpr int NS = 16 / R;   // load instructions (1 KiB each) per record
@@ -155,10 +148,7 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WPE > 0
                 const uint32_t k = (uint32_t)(64 * s + wl);
                 const uint32_t o = k < nload[j] ? 16u * k : 0x80000000u;
                 if ((NTS == 32 || (HINT >= 1 && HINT <= 7)) && s == 0) {  // some header lanes with the default cache policy
-                    // HINT 1 (and NTS 32): the segments of record offsets [10, 28) (an IPv4 record's fields);
-                    // 2: those of [0, 64); 3: the whole 256-B window; 4: the segment of offset 10 only;
-                    // 5: the 16-B chunk of offset 10 only; 6: the segment of the record's first byte;
-                    // 7: the line's first segment (lanes 0-3)
+                    // (XwalkHint 1-7; NTS 32 takes hint 1's lanes)
                     const uint32_t sg = (uint32_t)wl >> 2, h = head[j];
                     const bool c = (HINT == 0 || HINT == 1) ? (sg == (h + 10u) >> 6 || sg == (h + 27u) >> 6)
                                    : HINT == 2 ? (sg == h >> 6 || sg == (h + 63u) >> 6)
@@ -170,8 +160,7 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WPE > 0
                     if (c) v[s][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, o, soff, 0);
                     else v[s][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, o, soff, 2);
                 } else if ((HINT == 8 && s == 0) || (HINT == 9 && s == 1) || HINT == 10) {
-                    // 8: instruction 0 split in two (lanes 0-3 / the rest), both non-temporal; 9: lanes 0-3 of
-                    // instruction 1 with the default policy; 10: lanes 0-3 of every instruction
+                    // (XwalkHint 8-10)
                     if (wl < 4) v[s][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, o, soff, HINT == 8 ? 2 : 0);
                     else v[s][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, o, soff, 2);
                 } else if (((NTS == 4 || NTS == 5) && s == 0) || NTS == 8) v[s][j] = __builtin_amdgcn_raw_buffer_load_b128(rs, o, soff, 0);
@@ -365,187 +354,39 @@ __global__ __launch_bounds__(64 * WV) __attribute__((amdgpu_waves_per_eu(WPE > 0
     }
 }
 
-// records per wavefront for a record length (0: not served)
-static int xwalk_records(uint32_t len) {
-    if (len < 1024) return 0;
-    for (int R = 8; R >= 1; R /= 2)
-        if (len <= 1024u * (16 / R) - 127u) return R;
-    return 0;
+// One form at R records per wavefront.  The launch geometry is the form's: 64 * WV threads, a grid of
+// one workgroup per WV * STEPS wavefronts' records (`blocks` counts workgroups of xwalk::WAVES
+// wavefronts), PERSIST capped at the resident workgroups; a form that exists at one R or up to a
+// length only (HALF, WV = 8) gives way to XPlain elsewhere.
+template <int MODE, int R, class F>
+static void launch_xwalk_form(uint32_t blocks, const KParams& p, hipStream_t s) {
+    if constexpr (F::ONLY_R != 0 && F::ONLY_R != R) {
+        launch_xwalk_form<MODE, R, XPlain>(blocks, p, s);
+    } else {
+        if (p.len > F::MAX_LEN) return launch_xwalk_form<MODE, R, XPlain>(blocks, p, s);
+        constexpr uint32_t per = (uint32_t)(F::WV / xwalk::WAVES * F::STEPS);
+        uint32_t b = (blocks + per - 1) / per;
+        if constexpr (F::PERSIST) {
+            const uint32_t cap = resident_blocks((const void*)xwalk_kernel<MODE, R, F>, p.num_cu ? p.num_cu : 256u, b);
+            b = b < cap ? b : cap;
+        }
+        hipLaunchKernelGGL((xwalk_kernel<MODE, R, F>), dim3(b), dim3(64 * F::WV), 0, s, p);
+    }
 }
 
+// (variant, mode) -> form: the registry's switch (csum_variants.h with_xwalk_form).
 template <int R>
-static void launch_xwalk_r(int mode, int variant, uint32_t blocks, const KParams& p, hipStream_t s) {
-#ifdef SMOL_EXP
-    if (mode == MODE_EMIT && staged_variant(variant)) {  // the staging launch (the segment pass follows)
-        if (variant == 80) hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 32, false, true>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 0, false, true>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 82 || variant == 83) {  // round 6: the field-segment lines loaded cached (HINT); 82 verify / 47's
-                                          // emit, 83 = 57 (nt segment stores) + the hint
-        if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 1>), dim3(blocks), dim3(256), 0, s, p);
-        else if (variant == 83) hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 1, false, false, 1>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 0, false, false, 1>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 113 && mode == MODE_VERIFY) {  // 89 with two tiles per workgroup (64 records at R = 8)
-        hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 7, 0, xwalk::WAVES, 2>), dim3((blocks + 1) / 2),
-                           dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 113 && mode == MODE_EMIT) {  // 101 with two tiles per workgroup
-        hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 65, false, false, 0, 0, xwalk::WAVES, 2>), dim3((blocks + 1) / 2),
-                           dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 108 && mode == MODE_VERIFY) {  // 89 with the status bytes stored non-temporal (NTS 128)
-        hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 128, false, false, 7>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 107 && mode == MODE_VERIFY && R == 8) {  // 89 in 512-thread workgroups (64 records, 64 status bytes)
-        hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 7, 0, 8>), dim3((blocks + 1) / 2),
-                           dim3(512), 0, s, p);
-        return;
-    }
-    if ((variant == 110 || variant == 112) && mode == MODE_EMIT) {  // 101 + first-load hint 7 (110) / 1 (112); verify: 89
-        if (variant == 110) hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 65, false, false, 7>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 65, false, false, 1>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if ((variant == 110 || variant == 112) && mode == MODE_VERIFY) {
-        hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 7>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if ((variant == 107 || variant == 108) && mode == MODE_EMIT) {  // (107's / 108's emit: 101)
-        hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 65>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 106 && mode == MODE_VERIFY) {  // 89 without its status stores (timing only, experiments build)
-        hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, true, false, false, 0, false, false, 7>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 100) {  // round 6: 57 with the segments stored sc0 sc1 nt (101: sc1 nt, the product's); verify: 89
-        if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 7>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 64>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 93 || variant == 99) {  // round 6: 89 / 57 held to 5 (93) or 6 (99) wavefronts per SIMD
-        if (variant == 93) {
-            if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 7, 5>), dim3(blocks), dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 1, false, false, 0, 5>), dim3(blocks), dim3(256), 0, s, p);
-        } else {
-            if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 7, 6>), dim3(blocks), dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 1, false, false, 0, 6>), dim3(blocks), dim3(256), 0, s, p);
-        }
-        return;
-    }
-    if (variant >= 90 && variant <= 92) {  // verify hint forms 8-10 (emit: 57)
-        if (mode == MODE_VERIFY) {
-            if (variant == 90) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 8>), dim3(blocks), dim3(256), 0, s, p);
-            else if (variant == 91) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 9>), dim3(blocks), dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 10>), dim3(blocks), dim3(256), 0, s, p);
-        } else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 1>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant >= 84 && variant <= 88) {  // verify hint forms 2-6 (emit: 57 with the same hint)
-        if (mode == MODE_VERIFY) {
-            switch (variant) {
-                case 84: hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 2>), dim3(blocks), dim3(256), 0, s, p); break;
-                case 85: hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 3>), dim3(blocks), dim3(256), 0, s, p); break;
-                case 86: hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 4>), dim3(blocks), dim3(256), 0, s, p); break;
-                case 87: hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 5>), dim3(blocks), dim3(256), 0, s, p); break;
-                default: hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 6>), dim3(blocks), dim3(256), 0, s, p); break;
-            }
-        } else {
-            switch (variant) {
-                case 86: hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 1, false, false, 4>), dim3(blocks), dim3(256), 0, s, p); break;
-                case 87: hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 1, false, false, 5>), dim3(blocks), dim3(256), 0, s, p); break;
-                default: hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 1, false, false, 1>), dim3(blocks), dim3(256), 0, s, p); break;
-            }
-        }
-        return;
-    }
-    if constexpr (R == 8) {
-        if (variant == 59 && p.len <= 1409) {
-            if (mode == MODE_VERIFY)
-                hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, 8, false, false, false, 0, true>), dim3(blocks), dim3(256), 0, s, p);
-            else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, 8, false, true, false, 0, true>), dim3(blocks), dim3(256), 0, s, p);
-            return;
-        }
-    }
-    if (variant == 15) {
-        if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 5>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 46) {
-        if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 16>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 43) {
-        if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 8>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 8>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 58) {
-        if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 2>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 45) {
-        if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 4>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-    if (variant == 48) {  // persistent, next step's loads ahead (the resident workgroups)
-        const uint32_t cap = mode == MODE_VERIFY
-                                 ? resident_blocks((const void*)xwalk_kernel<MODE_VERIFY, R, false, false, true>,
-                                                   p.num_cu ? p.num_cu : 256u, blocks)
-                                 : resident_blocks((const void*)xwalk_kernel<MODE_EMIT, R, false, true, true>,
-                                                   p.num_cu ? p.num_cu : 256u, blocks);
-        const uint32_t b = blocks < cap ? blocks : cap;
-        if (mode == MODE_VERIFY) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, true>), dim3(b), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, true>), dim3(b), dim3(256), 0, s, p);
-        return;
-    }
-#endif
-    const bool seg = variant % 64 == 47 || variant == 57 || variant == 89 || variant == 101;
-    if (mode == MODE_VERIFY) {  // (57: 47's verify; 101: 89's)
-        // 89 (round 6): lanes 0-3 of each record's first instruction (the first 64 B of its first line)
-        // load with the default cache policy, the rest non-temporal: C2 verify 0.2342 -> 0.2259 ms
-        // (bench lines interleaved on one box, profiles/r06_experiments/verify_hint_ab.txt); the split
-        // itself without the policy change (90) gains nothing
-        if (variant == 89 || variant == 101) hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false, false, 0, false, false, 7>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_VERIFY, R, false, false>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-#ifdef SMOL_EXP
-    // 64 + 44 / 64 + 47: stores compiled out (timing only); the numbers from 80 up are round-6 forms
-    if (variant == 64 + 44 || variant == 64 + 47) {
-        if (seg) hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, true, true>), dim3(blocks), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, true, false>), dim3(blocks), dim3(256), 0, s, p);
-        return;
-    }
-#endif
-    // 101 (late round 6): 57's segments stored write-through (sc1 nt): C2 emit 0.3089-0.3102 ->
-    // 0.3061-0.3064 ms, C4 0.2728-0.2739 -> 0.2682-0.2689 ms (bench lines interleaved on one box,
-    // profiles/r06_experiments/writethrough_segments_ab.txt)
-    if (variant == 101) hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 65>), dim3(blocks), dim3(256), 0, s, p);
-    else if (variant == 57 || variant == 89) hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true, false, 1>), dim3(blocks), dim3(256), 0, s, p);
-    else if (seg) hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, true>), dim3(blocks), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((xwalk_kernel<MODE_EMIT, R, false, false>), dim3(blocks), dim3(256), 0, s, p);
-}
-
-bool xwalk_fits(const KParams& p) {
-    // the buffer offsets of a wavefront's records stay below 2^31
-    return p.desc == nullptr && p.stride >= p.len && p.stride <= (1ull << 26) && xwalk_records(p.len) > 0;
+static bool launch_xwalk_r(int mode, int variant, uint32_t blocks, const KParams& p, hipStream_t s) {
+    if (mode == MODE_EMIT) return with_xwalk_form<true>(variant, [&](auto f) { launch_xwalk_form<MODE_EMIT, R, decltype(f)>(blocks, p, s); });
+    return with_xwalk_form<false>(variant, [&](auto f) { launch_xwalk_form<MODE_VERIFY, R, decltype(f)>(blocks, p, s); });
 }
 
 hipError_t launch_xwalk(int mode, int variant, const KParams& p, hipStream_t s) {
     const int R = xwalk_records(p.len);
     if (R == 0) return hipErrorInvalidValue;
     const uint64_t per = (uint64_t)xwalk::WAVES * R;
+    const bool staged = mode == MODE_EMIT && variant_is(variant, V_STAGED);
+    if (staged && (!p.stage || !p.stage_flags || p.n > kStageChunk)) return hipErrorInvalidValue;
     note_launch(KERN_XWALK, (uint32_t)variant, 64 / R, 16 / R);
     // one workgroup per 4R records and no grid-stride loop: a batch past kMaxGridBlocks workgroups
     // (more records than 288 GB of HBM holds at these lengths) goes out as several launches
@@ -556,21 +397,20 @@ hipError_t launch_xwalk(int mode, int variant, const KParams& p, hipStream_t s) 
         q.buf = p.buf + i0 * p.stride;
         if (p.status) q.status = p.status + i0;
         const uint32_t b = grid_blocks((q.n + per - 1) / per, kMaxGridBlocks);
+        bool known;
         switch (R) {
-            case 8: launch_xwalk_r<8>(mode, variant, b, q, s); break;
-            case 4: launch_xwalk_r<4>(mode, variant, b, q, s); break;
-            case 2: launch_xwalk_r<2>(mode, variant, b, q, s); break;
-            default: launch_xwalk_r<1>(mode, variant, b, q, s); break;
+            case 8: known = launch_xwalk_r<8>(mode, variant, b, q, s); break;
+            case 4: known = launch_xwalk_r<4>(mode, variant, b, q, s); break;
+            case 2: known = launch_xwalk_r<2>(mode, variant, b, q, s); break;
+            default: known = launch_xwalk_r<1>(mode, variant, b, q, s); break;
         }
+        if (!known) return hipErrorInvalidValue;  // not a transposed-walk variant of this library
         hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
-#ifdef SMOL_EXP
-        if (mode == MODE_EMIT && staged_variant(variant)) {
-            if (!q.stage || !q.stage_flags || q.n > kStageChunk) return hipErrorInvalidValue;
+        if (staged) {  // the segment pass follows the staging launch
             e = launch_seg_pass(q, s);
             if (e != hipSuccess) return e;
         }
-#endif
     }
     return hipSuccess;
 }

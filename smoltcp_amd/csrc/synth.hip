@@ -402,7 +402,7 @@ hipError_t launch_field_scatter(uint8_t* buf, uint64_t bytes, const uint64_t* ad
 // segment of the buffer (bit s % 32 of word s / 32), set for the segments emit writes.  An 8-KiB piece
 // is 128 segments = 4 bitmap words, read as one uniform (scalar) load; lane l's chunk of load u lies
 // in segment 16 u + l / 4 of the piece.  nt: the segments stored non-temporal (emit's form for packed
-// 1400-1580-B records, csum_api.cpp xwalk_auto).  The tail past the last whole piece is read, not
+// 1400-1580-B records, csum_dispatch.h xwalk_auto).  The tail past the last whole piece is read, not
 // written.
 template <bool NT>
 __global__ __launch_bounds__(256) void segment_probe_kernel(uint8_t* buf, uint64_t n16, const uint32_t* bitmap) {

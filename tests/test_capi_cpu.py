@@ -167,3 +167,80 @@ def test_dispatch_table_matches_sweeps():
     assert fixed_launch("verify", 1500, 1500) == ("xwalk_kernel", 89)
     assert fixed_launch("emit", 1500, 1500) == ("xwalk_kernel", 101)
     assert fixed_launch("verify", 1000, 1000) == ("csum_kernel", 5)
+
+
+def _both_libs():
+    assert os.path.exists(_lib.EXP_LIB_PATH), "build() makes the experiments library too"
+    return (("product", _lib.lib()), ("experiments", _lib.lib(_lib.EXP_LIB_PATH)))
+
+
+def test_dispatch_matches_recorded_dump():
+    """smol_csum_tool_pick (csum_dispatch.h pick_kernel) decides what the commit before the variant
+    registry decided.  tests/data/dispatch_dump_parent.txt.gz was recorded from that commit, never from
+    the code under test: its pick_kernel behind the same context-free entry, both of its libraries,
+    tests/dispatch_dump.py's grid (every built variant, desc_staged, a forced shape, the four ops, packed
+    / gapped by 1 / gapped by 64 / descriptor batches, SMOL_BATCH_FIELD_STORES, SMOL_REC_IPHDR_ONLY, NHC)
+    at lengths 64, 1500, 1922 and 9024, then run-length coded as text (the full 25-length dump was compared once, when the registry
+    went in)."""
+    from tests import dispatch_dump as D
+
+    want = list(D.recorded_lines(os.path.join(ROOT, "tests", "data", "dispatch_dump_parent.txt")))
+    got = [line for name, L in _both_libs() for line in D.dump_lines(L, name, D.RECORDED_LENGTHS)]
+    assert len(want) == 60416 and len(got) == len(want)
+    bad = [(w, g) for w, g in zip(want, got) if w != g]
+    assert not bad, (len(bad), bad[:5])
+
+
+def test_kernel_forms_match_recorded_table():
+    """The registry's (variant, mode) -> kernel form (smol_csum_tool_form: the switch the launchers
+    instantiate xwalk_kernel / dwalk_kernel through) is the one the commit before the registry launched.
+    tests/data/kernel_forms_parent.jsonl was recorded from that commit: its launch_xwalk and
+    launch_dwalk compiled for the host with the launch macro recording the kernel's template arguments,
+    grid and block, called for every variant, both modes and every R (100000 records of 1409, 1500,
+    1922, 3970 and 8066 B), with and without SMOL_EXP, normalised to named values and restricted to the
+    (variant, mode) pairs that commit's dispatch could deliver.  Its product rows no longer include the
+    staged forms of 94 / 95 / 96, which the product library never ran."""
+    import json
+
+    with open(os.path.join(ROOT, "tests", "data", "kernel_forms_parent.jsonl")) as f:
+        want = [json.loads(line) for line in f]
+    xnames = ["NOSTORE", "SEG", "PERSIST", "NTS", "HALF", "STAGE", "HINT", "WPE", "WV", "STEPS"]
+    plain = dict(zip(xnames, [0, 0, 0, 0, 0, 0, 0, 0, 4, 1]))
+    out = (ctypes.c_int * 13)()
+    info = (ctypes.c_int * 4)()
+    for name, L in _both_libs():
+        rows = [r for r in want if r["lib"] == name]
+        assert rows
+        seen = set()
+        for r in rows:
+            op = 1 if r["mode"] == "emit" else 2
+            assert r["kernel_mode"] == r["mode"]
+            assert L.smol_csum_tool_form(r["variant"], op, out) == 0, (name, r["variant"], r["mode"])
+            seen.add((r["variant"], op))
+            then = [t["kernel"] for t in r["then"]]
+            if r["family"] == "xwalk":
+                assert out[0] == 2
+                form = dict(zip(xnames, out[1:11]))
+                only_r, max_len = out[11], out[12]
+                if (only_r and only_r != r["R"]) or (max_len and r["len"] > max_len):
+                    form = plain
+                assert form == r["form"], (name, r["variant"], r["mode"], r["len"], form, r["form"])
+                assert r["block"] == 64 * form["WV"]
+                if not form["PERSIST"]:
+                    wgs = -(-100000 // (4 * r["R"]))
+                    assert r["grid"] == -(-wgs // (form["WV"] // 4 * form["STEPS"]))
+                assert then == (["seg_pass4_kernel"] if form["STAGE"] else [])
+            else:
+                assert out[0] == 3
+                form = dict(zip(["NOSTORE", "GROUPS", "SEGF"], out[1:4]))
+                assert form == r["form"], (name, r["variant"], r["mode"], form, r["form"])
+                assert then == {-1: [], 0: ["seg_pass4_kernel"], 1: ["seg_pass_kernel"]}[out[4]]
+        # and the library has no form the recorded commit did not launch
+        for v in range(128):
+            for op in (1, 2):
+                if L.smol_csum_tool_form(v, op, out) == 0:
+                    assert (v, op) in seen, (name, v, op)
+                    assert L.smol_csum_tool_variant_info(v, info) == 0 and info[0] in (2, 3) and info[2] == 1
+    P = _lib.lib()
+    for v in (94, 95, 96):
+        assert P.smol_csum_tool_form(v, 1, out) == _lib.SMOL_EINVAL
