@@ -22,6 +22,9 @@
  *         Icmpv6Repr/IgmpRepr::emit under `caps` (fill when caps.X.tx(), else write 0);
  *       - smol_csum_batch_verify == the checksum gates of the matching Repr::parse under `caps`
  *         (verify when caps.X.rx()), reported as one status byte per record;
+ *       - smol_csum_batch_emit_fields == emit's values without the writes: one 16-byte entry per
+ *         record (field offsets, values, status) for a caller whose frames stay in host memory and
+ *         who patches them there with smol_csum_apply_fields;
  *       - smol_csum_batch_data   == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
@@ -250,6 +253,45 @@ typedef struct {
 int smol_csum_batch_copy_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* batch,
                               const uint8_t* d_src, const smol_csum_copy_t* d_copy,
                               const smol_checksum_caps_t* caps, uint8_t* d_status, void* stream);
+
+/* ---- emit_fields: checksum values out, frames patched on the host ------------------------- */
+
+#define SMOL_NO_FIELD 0xffffu
+/* One record's emit result (16 bytes, 16-byte aligned device array). */
+typedef struct {
+    uint16_t off[3];   /* record-relative byte offset of [0] the IPv4 header checksum, [1] the L4 checksum,
+                          [2] the embedded IPv4 header checksum of an ICMPv4 error message; SMOL_NO_FIELD: none */
+    uint16_t val[3];   /* the value smol_csum_batch_emit would write there (numeric; goes out big-endian); 0 when none */
+    uint8_t status;    /* the byte smol_csum_batch_emit puts in d_status (MALFORMED / UNSUPPORTED bits) */
+    uint8_t reserved[3]; /* 0 */
+} smol_csum_fields_t;
+
+/* Emit without the in-place writes.  In the reference the frame stays in host memory and every
+ * checksum write is two bytes: UdpPacket::fill_checksum (src/wire/udp.rs:194-208),
+ * TcpPacket::fill_checksum (src/wire/tcp.rs:616-626), Ipv4Packet::fill_checksum
+ * (src/wire/ipv4.rs:506-513), Icmpv4Repr::emit (src/wire/icmpv4.rs:520-554).  This call gives the
+ * offload that shape: the device reads the frames (a copy of the TxToken::consume buffers) and returns
+ * only the fields, so nothing but 16 bytes per frame has to come back over the host link.
+ *
+ * For every record, d_fields[i] holds exactly the fields smol_csum_batch_emit would write under
+ * `caps`, with the same values: the IPv4 header checksum (0 when caps.ipv4 has no tx()), the L4
+ * checksum (UDP 0 -> 0xffff, IGMP always filled), an ICMPv4 error message's embedded IPv4 header
+ * checksum (with the ICMP checksum computed over that new value), the header alone for a
+ * SMOL_REC_IPHDR_ONLY record, and for malformed / unsupported records the same fields and status bits
+ * as emit.  Unused slots hold off = SMOL_NO_FIELD, val = 0.  Nothing is written to d_buf.
+ * SMOL_BATCH_FIELD_STORES has no meaning here and is accepted.  The call uses no context scratch, no
+ * event and no allocation; it is stream-ordered on `stream`, and calls on different streams are
+ * independent (also on one context).  SMOL_EINVAL: NULL ctx, bad caps, NULL or misaligned d_fields
+ * with n > 0.  Not covered: the 6LoWPAN NHC entry points (no address array here) and IPv4 fragment
+ * groups (smol_csum_batch_emit_frag).
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive); a loader that must run
+ * against an older build probes for the symbol (dlsym). */
+int smol_csum_batch_emit_fields(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
+                                const smol_checksum_caps_t* caps, smol_csum_fields_t* d_fields, void* stream);
+
+/* host: write the entry's fields into one record; SMOL_ERANGE (nothing written) if a field does not fit in len */
+int smol_csum_apply_fields(uint8_t* rec, uint32_t len, const smol_csum_fields_t* f);
 
 /* ---- 3. IPv4 fragment groups ------------------------------------------------------------- */
 

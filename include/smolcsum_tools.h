@@ -88,6 +88,13 @@ int smol_csum_tool_set_xcd_remap(smol_csum_ctx_t* ctx, int on);
  * kernel launches of at most `records` records each, on the same stream. */
 int smol_csum_tool_set_launch_records(smol_csum_ctx_t* ctx, uint64_t records);
 
+/* The kernel form smol_csum_batch_emit_fields runs: 0 the library's choice (csum_dispatch.h pick_fields),
+ * 1 the walk kernel (any batch), 2 the transposed walk (fixed-stride records of 1024-16257 B), 3 the
+ * descriptor walk (descriptor batches).  A forced form that does not serve the batch gives way to the
+ * walk kernel.  smol_csum_tool_set_variant does not reach this call: the three forms have no variant
+ * number. */
+int smol_csum_tool_set_fields_kernel(smol_csum_ctx_t* ctx, int kernel);
+
 /* Read-only HBM streaming probe over `bytes` (multiple of 16, 16-byte aligned `d_buf`): the
  * achievable read ceiling that the checksum kernels are compared with.  Each wavefront streams
  * contiguous 8-KiB pieces with eight non-temporal 16-byte loads per lane in flight (the fastest
@@ -164,7 +171,8 @@ const char* smol_csum_tool_kernel_name(const smol_csum_ctx_t* ctx, int op, int h
 /* The kernel instantiation of this process's last checksum launch (any context), packed as
  * kernel << 24 | variant << 16 | G << 8 | U; kernel 1 = csum_kernel, 2 = csum_tile_kernel,
  * 3 = copy_kernel, 4 = csum_kernel with the 6LoWPAN NHC gates, 5 = xwalk_kernel, 6 = dwalk_kernel;
- * 0 before the first launch. */
+ * smol_csum_batch_emit_fields (variant 0): 7 = csum_fields_kernel, 8 = xwalk_kernel with the fields sink,
+ * 9 = dwalk_kernel with it; 0 before the first launch. */
 uint32_t smol_csum_tool_last_launch(void);
 
 /* 1 when this build of the library runs kernel variant `variant` (smol_csum_tool_set_variant), else

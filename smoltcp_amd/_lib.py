@@ -30,7 +30,8 @@ ABI_SYMBOLS = [
     "smol_csum_data", "smol_csum_combine", "smol_csum_pseudo_header_v4",
     "smol_csum_pseudo_header_v6", "smol_csum_pseudo_header", "smol_csum_ctx_create",
     "smol_csum_ctx_destroy", "smol_csum_batch_data", "smol_csum_batch_emit",
-    "smol_csum_batch_verify", "smol_csum_batch_copy_emit", "smol_csum_batch_emit_frag",
+    "smol_csum_batch_verify", "smol_csum_batch_copy_emit", "smol_csum_batch_emit_fields",
+    "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
     "smol_csum_batch_verify_frag", "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
 ]
@@ -44,11 +45,13 @@ TOOL_SYMBOLS = [
     "smol_csum_tool_variant_built",
     "smol_csum_tool_kernel_name", "smol_csum_tool_kernel_for", "smol_csum_tool_last_launch",
     "smol_csum_tool_pick", "smol_csum_tool_variant_info", "smol_csum_tool_form",
+    "smol_csum_tool_set_fields_kernel",
 ]
 # Tool symbols added in later rounds: bound only when the loaded build has them (SMOLCSUM_LIB may name
 # an older build for an A/B run), and a call to a missing one raises AttributeError naming it.
 OPTIONAL_TOOL_SYMBOLS = ("smol_csum_tool_variant_built", "smol_csum_tool_kernel_for", "smol_csum_tool_segment_probe",
-                         "smol_csum_tool_pick", "smol_csum_tool_variant_info", "smol_csum_tool_form")
+                         "smol_csum_tool_pick", "smol_csum_tool_variant_info", "smol_csum_tool_form",
+                         "smol_csum_tool_set_fields_kernel")
 
 
 class SmolError(RuntimeError):
@@ -84,6 +87,19 @@ class BatchC(ctypes.Structure):
         ("reserved", ctypes.c_uint8 * 2),
     ]
 
+
+class FieldsC(ctypes.Structure):
+    """smol_csum_fields_t: one record's emit result (smol_csum_batch_emit_fields)."""
+
+    _fields_ = [
+        ("off", ctypes.c_uint16 * 3),
+        ("val", ctypes.c_uint16 * 3),
+        ("status", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 3),
+    ]
+
+
+NO_FIELD = 0xFFFF  # SMOL_NO_FIELD
 
 _LIBS = {}
 
@@ -131,6 +147,12 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         f = getattr(L, name)
         f.argtypes = [vp, vp, ctypes.POINTER(BatchC), vp, ctypes.POINTER(Caps), vp, vp]
         f.restype = i32
+    # added within ABI 6: an older build named by SMOLCSUM_LIB may lack them
+    if hasattr(L, "smol_csum_batch_emit_fields"):
+        L.smol_csum_batch_emit_fields.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps), vp, vp]
+        L.smol_csum_batch_emit_fields.restype = i32
+        L.smol_csum_apply_fields.argtypes = [vp, u32, ctypes.POINTER(FieldsC)]
+        L.smol_csum_apply_fields.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []
@@ -172,6 +194,7 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         "smol_csum_tool_pick": ([i32, i32, i32, i32, ctypes.POINTER(BatchC), i32, ctypes.POINTER(i32)], i32),
         "smol_csum_tool_variant_info": ([i32, ctypes.POINTER(i32)], i32),
         "smol_csum_tool_form": ([i32, i32, ctypes.POINTER(i32)], i32),
+        "smol_csum_tool_set_fields_kernel": ([vp, i32], i32),
     }
     assert set(optional) == set(OPTIONAL_TOOL_SYMBOLS)
     for name in OPTIONAL_TOOL_SYMBOLS:

@@ -45,6 +45,7 @@ struct smol_csum_ctx {
     bool sample_pending;
     int desc_staged;          // 1: the staged form (also before any sample), 0: in place
     uint32_t since_probe;
+    int fields_kernel;        // emit_fields: FK_AUTO, or a forced form (smol_csum_tool_set_fields_kernel)
 };
 
 namespace {
@@ -327,6 +328,7 @@ int smol_csum_ctx_create(int device, smol_csum_ctx_t** out) {
     c->sample_pending = false;
     c->desc_staged = 1;
     c->since_probe = 0;
+    c->fields_kernel = FK_AUTO;
     c->tile_records = 32;
     c->max_blocks_set = false;
     c->xcd_remap = -1;
@@ -392,6 +394,52 @@ int smol_csum_batch_copy_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_c
     if (rc != SMOL_OK || b->n == 0) return rc;
     if (!d_src || !d_copy || ((uintptr_t)d_copy & 15u) != 0) return SMOL_EINVAL;
     return run(ctx, MODE_COPY, d_buf, b, caps, nullptr, d_status, stream, d_src, d_copy);
+}
+
+// Emit with the fields sink (include/smolcsum.h): every record's entry to d_fields, nothing into d_buf.
+// Uses none of the context's scratch or events, so calls on different streams are independent.
+int smol_csum_batch_emit_fields(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
+                                const smol_checksum_caps_t* caps, smol_csum_fields_t* d_fields, void* stream) {
+    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
+    int rc = check_batch(b, d_buf);
+    if (rc != SMOL_OK || b->n == 0) return rc;
+    if (!d_fields || ((uintptr_t)d_fields & 15u) != 0) return SMOL_EINVAL;
+    KParams p;
+    std::memset(&p, 0, sizeof p);
+    p.buf = const_cast<uint8_t*>(d_buf);  // (the fields sink stores nothing there)
+    p.stride = b->stride;
+    p.len = b->len;
+    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
+    p.caps_ipv4 = caps->ipv4;
+    p.caps_udp = caps->udp;
+    p.caps_tcp = caps->tcp;
+    p.caps_icmpv4 = caps->icmpv4;
+    p.caps_icmpv6 = caps->icmpv6;
+    p.dummy = ctx->dummy;
+    p.num_cu = ctx->max_blocks_set ? 0u : (uint32_t)(ctx->num_cu > 0 ? ctx->num_cu : 256);
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
+    const hipStream_t s = (hipStream_t)stream;
+    // launch_records: consecutive launches, the entries advancing with the records
+    const uint64_t per = ctx->launch_records && ctx->launch_records < b->n ? ctx->launch_records : b->n;
+    for (uint64_t i0 = 0; i0 < b->n; i0 += per) {
+        p.n = b->n - i0 < per ? b->n - i0 : per;
+        p.desc = b->desc ? b->desc + i0 : nullptr;
+        if (!b->desc) p.buf = const_cast<uint8_t*>(d_buf) + i0 * b->stride;
+        p.fields = d_fields + i0;
+        hipError_t e;
+        switch (pick_fields(ctx->fields_kernel, b, p)) {
+            case FK_XWALK: e = launch_xwalk_fields(p, s); break;
+            case FK_DWALK: e = launch_dwalk_fields(p, s); break;
+            default:
+                // the walk kernel on variant 5's shape (kWalkVerify: the line grid)
+                e = b->desc ? launch_walk_fields<false>(auto_shape(b->len, true, kWalkVerify), p, ctx->max_blocks, s)
+                            : launch_walk_fields<true>(auto_shape(b->len, false, kWalkVerify), p, ctx->max_blocks, s);
+                break;
+        }
+        if (e != hipSuccess) return hip_fail(e, "emit_fields kernel launch");
+    }
+    return SMOL_OK;
 }
 
 // ---- IPv4 fragment groups ---------------------------------------------------------------------
@@ -528,6 +576,12 @@ int smol_csum_tool_set_xcd_remap(smol_csum_ctx_t* ctx, int on) {
 int smol_csum_tool_set_launch_records(smol_csum_ctx_t* ctx, uint64_t records) {
     if (!ctx) return SMOL_EINVAL;
     ctx->launch_records = records;
+    return SMOL_OK;
+}
+
+int smol_csum_tool_set_fields_kernel(smol_csum_ctx_t* ctx, int kernel) {
+    if (!ctx || kernel < FK_AUTO || kernel > FK_DWALK) return SMOL_EINVAL;
+    ctx->fields_kernel = kernel;
     return SMOL_OK;
 }
 

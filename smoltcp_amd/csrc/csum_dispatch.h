@@ -196,6 +196,30 @@ inline bool family_serves(const Variant& r, int mode, const KParams& p) {
     }
 }
 
+// ---- emit_fields (smol_csum_batch_emit_fields) -----------------------------------------------------
+// Its three forms live outside the registry (set_variant does not reach them).  Measured (tools/exp_fields.py,
+// one box, the forms interleaved; profiles/fields_kernels.json):
+//  - fixed strides: the transposed walk from 1280 B up to its last length (16257 B).  Per length, packed and
+//    with 64-B gaps, transposed / walk: 1024-1216 B 1.01-1.07 (the walk kernel wins), 1320-1500 B 0.94-0.99,
+//    1921-6000 B 0.47-0.87 (the walk kernel's 32 x 4 / 64 x 4 shapes idle half their lanes there), 9000 B
+//    0.93-0.95, 1664 / 8065 / 12000 / 16000 B within 2 % either way.  Verify's table differs (C4's 1320 B: verify
+//    takes the walk kernel, 0.209 against 0.226 ms; here the transposed form wins, 0.219 against 0.237 ms):
+//    its finishing lanes write one 128-B line of entries per wavefront where verify writes 8 status bytes;
+//  - descriptor batches: the descriptor walk (C3: 0.703 ms against the walk kernel's 0.932);
+//  - everything else (records under 1280 B or past 16257 B, strides past 64 MiB): the walk kernel.
+// `forced` (smol_csum_tool_set_fields_kernel): a form that does not serve the batch gives way to the walk
+// kernel.
+constexpr uint32_t kFieldsXwalkMinLen = 1280;
+enum FieldsKernel { FK_AUTO = 0, FK_WALK = 1, FK_XWALK = 2, FK_DWALK = 3 };
+inline int pick_fields(int forced, const smol_csum_batch_t* b, const KParams& p) {
+    const bool x_ok = xwalk_fits(p), d_ok = p.desc != nullptr && dwalk_fits(p);
+    if (forced == FK_XWALK) return x_ok ? FK_XWALK : FK_WALK;
+    if (forced == FK_DWALK) return d_ok ? FK_DWALK : FK_WALK;
+    if (forced == FK_WALK) return FK_WALK;
+    if (x_ok && b->len >= kFieldsXwalkMinLen) return FK_XWALK;
+    return d_ok ? FK_DWALK : FK_WALK;
+}
+
 inline Pick pick_kernel(const PickCtx& ctx, int mode, const smol_csum_batch_t* b, const KParams& p) {
     const bool has_desc = b->desc != nullptr;
     const bool nhc = p.addrs != nullptr;

@@ -399,7 +399,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & (DW
             if (wsB != ~0ull && lane < 8) seg_store(wsB + 8u * (uint32_t)lane);
         }
     } else {
-        if (mine) finish_gates<G, MODE, false, decltype(rd), 0, false, NOSTORE, (SEGF & DW_FIELDS_NT) != 0>(p, g, a1, rd, winb, hd, a0, r, lane);
+        if (mine) finish_gates<G, MODE, false, decltype(rd), 0, false, NOSTORE, (SEGF & DW_FIELDS_NT) != 0, false,
+                               EMIT && (SEGF & DW_FIELDS_OUT) != 0>(p, g, a1, rd, winb, hd, a0, r, lane);
     }
 }
 
@@ -516,6 +517,26 @@ static hipError_t launch_dwalk_form(const KParams& p, hipStream_t s) {
         if (e != hipSuccess || F::SEGPASS < 0) return e;
         return launch_seg_pass(p, s, F::SEGPASS);
     }
+}
+
+// emit_fields' descriptor form: variant 63's read form (each group streams its record, the header windows
+// loaded with the default cache policy) with the fields sink; a wavefront's 8 entries are one 128-B line.
+hipError_t launch_dwalk_fields(const KParams& p, hipStream_t s) {
+    if (!p.fields) return hipErrorInvalidValue;
+    note_launch(KERN_DWALK_FIELDS, 0, dwalk::G, dwalk::U);
+    const uint64_t span = kMaxGridBlocks * (uint64_t)dwalk::GPB;
+    for (uint64_t i0 = 0; i0 < p.n; i0 += span) {
+        KParams q = p;
+        q.n = p.n - i0 < span ? p.n - i0 : span;
+        if (p.desc) q.desc = p.desc + i0;
+        else q.buf = p.buf + i0 * p.stride;
+        q.fields = p.fields + i0;
+        const uint32_t b = grid_blocks((q.n + dwalk::GPB - 1) / dwalk::GPB, kMaxGridBlocks);
+        hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, DW_WIN_CACHED | DW_FIELDS_OUT>), dim3(b), dim3(256), 0, s, q);
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_dwalk(int mode, int variant, const KParams& p, hipStream_t s) {

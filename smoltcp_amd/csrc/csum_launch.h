@@ -55,6 +55,7 @@ struct KParams {
                            // xcd_block(b); K >= 2: those of xcd_chunk(b, K) (see below)
     uint64_t* stage;       // staged emit (csum_walk.h stage_entry): one 8-B field entry per record
     uint32_t* stage_flags; // staged emit: one flag per 8 records (1: their entries are this call's)
+    smol_csum_fields_t* fields;  // emit_fields: one 16-B entry per record (the kernels write nothing else)
 };
 
 // The 8 XCDs of an MI355X are dealt workgroups round-robin (MI355X_MICROARCH.md, workgroup dispatch:
@@ -88,7 +89,11 @@ __device__ inline uint64_t logical_block(uint32_t xcd_remap) {
 // The kernel instantiation of the process's last checksum launch, packed kernel << 24 | variant << 16
 // | G << 8 | U (smol_csum_tool_last_launch): tests check that a forced variant runs the kernel it
 // names rather than a dispatch fallback.
-enum { KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6 };
+// KERN_*_FIELDS: the three forms of smol_csum_batch_emit_fields (variant 0; they have no registry row).
+enum {
+    KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6,
+    KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9
+};
 inline std::atomic<uint32_t> g_last_launch{0};
 inline void note_launch(uint32_t kern, uint32_t var, uint32_t g, uint32_t u) {
     g_last_launch.store(kern << 24 | (var & 0xffu) << 16 | (g & 0xffu) << 8 | (u & 0xffu),
@@ -131,6 +136,14 @@ hipError_t launch_xwalk(int mode, int variant, const KParams& p, hipStream_t s);
 // build) writes the field segments whole.  Records per launch pair:
 constexpr uint64_t kStageChunk = 1ull << 21;
 hipError_t launch_seg_pass(const KParams& p, hipStream_t s, int form = 0);
+// emit_fields (smol_csum_batch_emit_fields): MODE_EMIT's parse and gates with the fields sink, each
+// record's 16-B entry to p.fields and nothing into the records.  Three forms outside the variant
+// registry (csum_dispatch.h pick_fields chooses): the walk kernel (csum_walk_fields_{fixed,desc}.hip), the
+// transposed walk (csum_xwalk.hip, form XFields) and the descriptor walk (csum_dwalk.hip).
+template <bool IMPLICIT>
+hipError_t launch_walk_fields(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s);
+hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s);
+hipError_t launch_dwalk_fields(const KParams& p, hipStream_t s);
 
 // Synthetic batches and fault injection (tools; include/smolcsum_tools.h).
 struct SynthParams {

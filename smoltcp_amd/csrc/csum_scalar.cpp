@@ -69,4 +69,19 @@ int smol_csum_pseudo_header(int src_family, const uint8_t* src, int dst_family,
     return SMOL_EINVAL;
 }
 
+// The host half of smol_csum_batch_emit_fields: the two-byte checksum writes of the reference's
+// fill_checksum (udp.rs:194-208, tcp.rs:616-626, ipv4.rs:506-513, icmpv4.rs:520-554) into a record that
+// stayed in host memory.  Every field is range-checked before the first byte is written.
+int smol_csum_apply_fields(uint8_t* rec, uint32_t len, const smol_csum_fields_t* f) {
+    if (!rec || !f) return SMOL_EINVAL;
+    for (int i = 0; i < 3; i++)
+        if (f->off[i] != SMOL_NO_FIELD && (uint32_t)f->off[i] + 2u > len) return SMOL_ERANGE;
+    for (int i = 0; i < 3; i++) {
+        if (f->off[i] == SMOL_NO_FIELD) continue;
+        rec[f->off[i]] = (uint8_t)(f->val[i] >> 8);
+        rec[f->off[i] + 1] = (uint8_t)f->val[i];
+    }
+    return SMOL_OK;
+}
+
 }  // extern "C"

@@ -43,6 +43,7 @@ enum XwalkHint {
 // MAX_LEN does not hold.
 struct XPlain {
     static constexpr bool NOSTORE = false, SEG = false, PERSIST = false, HALF = false, STAGE = false;
+    static constexpr bool FIELDS = false;  // emit: the fields sink (XFields)
     static constexpr int NTS = NTS_PLAIN, HINT = HINT_NONE;
     static constexpr int WPE = 0;    // wavefronts per SIMD the kernel is held to (0: the compiler's)
     static constexpr int WV = 4;     // wavefronts per workgroup (8: 512 threads, half the grid)
@@ -71,6 +72,10 @@ struct XSegPersist : XSeg { static constexpr bool PERSIST = true; };
 struct XSegNoStore : XSeg { static constexpr bool NOSTORE = true; };
 struct XStage : XSeg { static constexpr bool STAGE = true; };
 struct XStageCached : XStage { static constexpr int NTS = NTS_STAGE_FIELDS_CACHED; };
+// emit_fields (smol_csum_batch_emit_fields): XPlain's emit reading like verify's 'h' form, every record's
+// 16-B entry to p.fields instead of its fields into the record.  No variants.def row: launch_xwalk_fields
+// runs it, outside the registry.
+struct XFields : XHint<HINT_LINE_HEAD> { static constexpr bool FIELDS = true; };
 
 // ---- dwalk_kernel's forms (csum_dwalk.hip) ----------------------------------------------------------
 enum DwalkSegf {
@@ -85,6 +90,7 @@ enum DwalkSegf {
     DW_FIRST = 256,         // the wavefront's first record may stage too (97)
     DW_GAPS = 512,          // staging over gapped / shuffled layouts (104)
     DW_ENTRIES_NT = 1024,   // entries and 2-B fields stored write-through non-temporal (109)
+    DW_FIELDS_OUT = 2048,   // emit_fields: the fields sink, nothing into the records (no registry row: launch_dwalk_fields)
 };
 struct DNone {  // the variant has no form of this mode (in this library)
     static constexpr bool NONE = true, NOSTORE = false, GROUPS = false;

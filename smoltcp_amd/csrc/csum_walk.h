@@ -469,8 +469,13 @@ __device__ __forceinline__ void stage_record(const KParams& p, uint64_t r, bool 
 // entry instead of the record (the caller has decided its segments go out whole in the segment pass:
 // no third field, both fields inside the LDS window); 2 stores the fields here and writes the entry
 // ~0; 0 stores them here (a wavefront that stages nothing).
+// FLD (smol_csum_batch_emit_fields, MODE_EMIT): the fields sink.  Lane 0 writes the record's 16-B entry
+// (smol_csum_fields_t: the offsets and values of the fields emit would write, the status byte) to
+// p.fields + r with one non-temporal 16-B store; nothing goes into the record and no status byte is
+// written.  The finishing lanes of a wavefront hold consecutive records, so their entries leave as one
+// contiguous run (8 records per wavefront: one 128-B line per store instruction).
 template <int G, int MODE, bool NHC, class RD, int WINB = 0, bool SEGP = false, bool NOSTORE = false,
-          bool NTST = false, bool STG = false>
+          bool NTST = false, bool STG = false, bool FLD = false>
 __device__ __forceinline__ void finish_gates(const KParams& p, const Geom& g, uint32_t acc, const RD& rd,
                                              const uint8_t* winb, uint32_t head, uint64_t a0, uint64_t r,
                                              int lane, uint8_t* winw = nullptr, uint64_t wsA = ~0ull,
@@ -610,7 +615,16 @@ __device__ __forceinline__ void finish_gates(const KParams& p, const Geom& g, ui
                 l4_ok = caps_rx(gate_caps) ? l4_valid : 1u;
             }
         }
-        if (EMITS && SEGP) {
+        if constexpr (FLD) {
+            static_assert(MODE == MODE_EMIT && !NHC && WINB == 0 && !SEGP && !STG, "the fields sink is emit's");
+            auto off = [](uint32_t f) { return f == MF_NONE ? (uint32_t)SMOL_NO_FIELD : (f & 0xffffu); };
+            u32x4 e;  // off[3], val[3], status, reserved[3]
+            e.x = off(fip) | off(fl4) << 16;
+            e.y = off(fin) | (vip & 0xffffu) << 16;
+            e.z = (vl4 & 0xffffu) | (vin & 0xffffu) << 16;
+            e.w = st & 0xffu;
+            __builtin_nontemporal_store(e, (GMEM u32x4*)((uint64_t)p.fields + 16ull * r));
+        } else if (EMITS && SEGP) {
             auto put = [&](uint32_t f, uint32_t v) {
                 const uint64_t x0 = (a0 + f) & ~63ull, x1 = (a0 + f + 1) & ~63ull;
                 const bool cov = (x0 == wsA || x0 == wsB) && (x1 == wsA || x1 == wsB);
@@ -691,7 +705,7 @@ __device__ __forceinline__ uint64_t shared_from(const KParams& p, uint64_t r, ui
 // and finish the record on its last step.  Returns false when the group has no more work.
 template <int G, int U, int MODE, bool IMPLICIT, bool NT, bool PF, bool SKIPD, bool LINE, bool NHC, int CU = 0,
           bool SHUF = false, bool WHOLE = false, bool SHUF2 = false, bool SEGW = false, bool SEGG = false,
-          bool SEGB = false, bool SEG6 = false, int SEGOPT = 0, int VAR = 0>
+          bool SEGB = false, bool SEG6 = false, int SEGOPT = 0, int VAR = 0, bool FLD = false>
 __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MODE == MODE_COPY>& cv,
                                           Regs<U, MODE == MODE_COPY>& nx, int lane, uint64_t ngroups, u32x4* win,
                                           int gib, SegInfo* si = nullptr, SegInfoG* sg = nullptr,
@@ -1130,7 +1144,8 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
                 if (sa != SEG_NONE) wsA = w.cur.a0 + (int64_t)sa;
                 if (sb != SEG_NONE) wsB = w.cur.a0 + (int64_t)sb;
             }
-            finish_gates<G, MODE, NHC, decltype(rd), ((COPY && WHOLE) || SEGF || SEGG) ? WIN : 0, SEGF || SEGG, NOSTORE>(
+            finish_gates<G, MODE, NHC, decltype(rd), ((COPY && WHOLE) || SEGF || SEGG) ? WIN : 0, SEGF || SEGG, NOSTORE,
+                         false, false, FLD>(
                 p, GREG ? w.gr : *w.g, w.acc, rd, winb, head, w.cur.a0, r, lane, reinterpret_cast<uint8_t*>(win),
                 wsA, wsB);
             if constexpr (SEGF || SEGG) {
@@ -1271,6 +1286,72 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MinWaves<VA
                                                             shared_from<G, MODE, IMPLICIT, LINE, VarT<VAR>::NOSHARE>(p, w.r, w.cur.a0, gib, ngroups));
             if (!walk_step<G, U, MODE, IMPLICIT, NT, PF, SKIPD, LINE, NHC, 0, SHUF, WHOLE, SHUF2, false, SEGG, SEGB, SEG6, 0, VAR>(
                     p, w, va, va, lane, ngroups, &win[gib][0], gib, nullptr, segg, blockwide)) break;
+        }
+    }
+}
+
+// emit_fields' walk form (smol_csum_batch_emit_fields, any batch): csum_kernel's variant-5 emit walk —
+// the line grid, non-temporal loads, the register prefetch and, over fixed strides, the shared
+// boundary lines (shared_from) — finishing through the fields sink (finish_gates FLD).  None of the
+// whole-segment machinery: it only shapes writes into the records, and this kernel writes none.
+template <int G, int U, bool IMPLICIT>
+__global__ __launch_bounds__(256) void csum_fields_kernel(KParams p) {
+    constexpr int VAR = 5;
+    static_assert(VarT<VAR>::NT && VarT<VAR>::PF && VarT<VAR>::LINE && !VarT<VAR>::SEGW && !VarT<VAR>::SEGG &&
+                      !VarT<VAR>::BSEG, "the walk's plain line-grid form");
+    constexpr int GPB = 256 / G;
+    __shared__ u32x4 win[GPB][Grid<true>::WIN_CH];
+    __shared__ Geom geo[GPB];
+    const int lane = (int)(threadIdx.x % G);
+    const int gib = (int)(threadIdx.x / G);
+    const uint64_t ngroups = (uint64_t)gridDim.x * GPB;
+    Walk w;
+    w.r = logical_block(p.xcd_remap) * GPB + gib;
+    if (w.r >= p.n) return;
+    w.cur = rec_at<IMPLICIT, false>(p, w.r);
+    w.nxt = rec_at<IMPLICIT, false>(p, w.r + ngroups < p.n ? w.r + ngroups : p.n - 1);
+    w.nch = n_chunks<true>(w.cur);
+    w.step = 0;
+    w.g = &geo[gib];
+    w.gr = Geom{};
+    w.s1 = 0;
+    w.acc = w.acc2 = 0;
+    w.fip = w.fl4 = w.fin = NO_FIELD;
+    w.far = false;
+    w.segA = w.segB = SEG_NONE;
+    Regs<U, false> va, vb;
+    load_step<G, U, true, false, true>(va, w.cur, w.nch, 0, lane, true, (uint64_t)p.dummy,
+                                       shared_from<G, MODE_EMIT, IMPLICIT, true>(p, w.r, w.cur.a0, gib, ngroups));
+    // the body is instantiated twice with the register sets' roles swapped (csum_kernel)
+    while (true) {
+        if (!walk_step<G, U, MODE_EMIT, IMPLICIT, true, true, IMPLICIT, true, false, 0, false, false, false, false, false,
+                       false, false, 0, VAR, true>(p, w, va, vb, lane, ngroups, &win[gib][0], gib)) break;
+        if (!walk_step<G, U, MODE_EMIT, IMPLICIT, true, true, IMPLICIT, true, false, 0, false, false, false, false, false,
+                       false, false, 0, VAR, true>(p, w, vb, va, lane, ngroups, &win[gib][0], gib)) break;
+    }
+}
+
+// The shapes auto_shape gives variant 5: fixed strides by record length, descriptors 16 x 3.
+template <int G, int U, bool IMPLICIT>
+hipError_t launch_fields_one(const KParams& p, uint32_t max_blocks, hipStream_t s) {
+    constexpr uint32_t GPB = 256 / G;
+    const uint32_t blocks = grid_blocks((p.n + GPB - 1) / GPB, max_blocks);
+    note_launch(KERN_WALK_FIELDS, 0, G, U);
+    hipLaunchKernelGGL((csum_fields_kernel<G, U, IMPLICIT>), dim3(blocks), dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+
+template <bool IMPLICIT>
+hipError_t launch_walk_fields(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s) {
+    if constexpr (!IMPLICIT) {
+        return launch_fields_one<16, 3, false>(p, max_blocks, s);
+    } else {
+        switch (shape) {
+            case CFG_G8U6: return launch_fields_one<8, 6, true>(p, max_blocks, s);
+            case CFG_G8U7: return launch_fields_one<8, 7, true>(p, max_blocks, s);
+            case CFG_G16U6: return launch_fields_one<16, 6, true>(p, max_blocks, s);
+            case CFG_G32U4: return launch_fields_one<32, 4, true>(p, max_blocks, s);
+            default: return launch_fields_one<64, 4, true>(p, max_blocks, s);
         }
     }
 }

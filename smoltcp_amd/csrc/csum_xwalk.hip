@@ -344,8 +344,8 @@ __global__ __launch_bounds__(64 * F::WV) __attribute__((amdgpu_waves_per_eu(F::W
         }
     } else {
         if (mine)
-            finish_gates<G, MODE, false, decltype(rd), 0, false, NOSTORE, (NTS & 128) != 0>(p, g, lane == 0 ? tot : 0u, rd,
-                                                                                           winb, hd, a0, r, lane);
+            finish_gates<G, MODE, false, decltype(rd), 0, false, NOSTORE, (NTS & 128) != 0, false, EMIT && F::FIELDS>(
+                p, g, lane == 0 ? tot : 0u, rd, winb, hd, a0, r, lane);
     }
     if (!more) break;
     wave_lds_sync();  // the windows are rewritten by the next step
@@ -372,6 +372,32 @@ static void launch_xwalk_form(uint32_t blocks, const KParams& p, hipStream_t s) 
         }
         hipLaunchKernelGGL((xwalk_kernel<MODE, R, F>), dim3(b), dim3(64 * F::WV), 0, s, p);
     }
+}
+
+// emit_fields' transposed form (XFields): R consecutive records finish in one wavefront, so their entries
+// leave as one run of R x 16 B (R = 8: a whole 128-B line per store instruction).
+hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s) {
+    const int R = xwalk_records(p.len);
+    if (R == 0 || !p.fields) return hipErrorInvalidValue;
+    const uint64_t per = (uint64_t)xwalk::WAVES * R;
+    note_launch(KERN_XWALK_FIELDS, 0, 64 / R, 16 / R);
+    const uint64_t span = kMaxGridBlocks * per;  // as launch_xwalk: no grid-stride loop
+    for (uint64_t i0 = 0; i0 < p.n; i0 += span) {
+        KParams q = p;
+        q.n = p.n - i0 < span ? p.n - i0 : span;
+        q.buf = p.buf + i0 * p.stride;
+        q.fields = p.fields + i0;
+        const uint32_t b = grid_blocks((q.n + per - 1) / per, kMaxGridBlocks);
+        switch (R) {
+            case 8: launch_xwalk_form<MODE_EMIT, 8, XFields>(b, q, s); break;
+            case 4: launch_xwalk_form<MODE_EMIT, 4, XFields>(b, q, s); break;
+            case 2: launch_xwalk_form<MODE_EMIT, 2, XFields>(b, q, s); break;
+            default: launch_xwalk_form<MODE_EMIT, 1, XFields>(b, q, s); break;
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 // (variant, mode) -> form: the registry's switch (csum_variants.h with_xwalk_form).

@@ -16,7 +16,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import BatchC, Caps, check, lib
+from ._lib import NO_FIELD, BatchC, Caps, FieldsC, check, lib
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -47,6 +47,38 @@ assert COPY_DTYPE.itemsize == 16
 FRAG_GROUP_DTYPE = np.dtype([("first", "<u8"), ("count", "<u4"), ("reserved", "<u4")])
 assert FRAG_GROUP_DTYPE.itemsize == 16
 MAX_FRAGMENTS = 256
+
+
+# smol_csum_fields_t: one record's emit result (smol_csum_batch_emit_fields)
+FIELDS_DTYPE = np.dtype([("off", "<u2", (3,)), ("val", "<u2", (3,)), ("status", "u1"), ("reserved", "u1", (3,))])
+assert FIELDS_DTYPE.itemsize == 16 == ctypes.sizeof(FieldsC)
+
+
+def apply_fields(host_buf: np.ndarray, record_offsets, record_lens, fields) -> np.ndarray:
+    """The host half of emit_fields, vectorised: write every entry's fields into its record of the
+    uint8 array `host_buf` (record i at record_offsets[i], record_lens[i] bytes; scalars broadcast),
+    big-endian, as smol_csum_apply_fields does per record.  `fields`: n entries, FIELDS_DTYPE or their
+    n x 16 uint8 view.  Returns a bool array: False where a field did not fit its record
+    (smol_csum_apply_fields' SMOL_ERANGE: nothing of that record is written)."""
+    f = np.ascontiguousarray(fields)
+    cols = np.ascontiguousarray(f.view(np.uint8).reshape(-1, 16).view("<u2")[:, :6].T)  # off[0..2], val[0..2]: contiguous
+    n = cols.shape[1]
+    offs = np.broadcast_to(np.asarray(record_offsets, dtype=np.int64), (n,))
+    lens = np.asarray(record_lens, dtype=np.int64)
+    lens = lens if lens.ndim == 0 else np.broadcast_to(lens, (n,))
+    have = cols[:3] != NO_FIELD
+    ok = ~(have & (cols[:3].astype(np.int32) + 2 > lens)).any(axis=0)
+    all_ok = bool(ok.all())
+    for j in range(3):  # one pass per slot, both bytes while the line is near: a record's fields never overlap
+        m = have[j] if all_ok else have[j] & ok
+        if not m.any():
+            continue
+        whole = bool(m.all())
+        pos = offs + cols[j] if whole else offs[m] + cols[j][m]
+        v = cols[3 + j] if whole else cols[3 + j][m]
+        host_buf[pos] = (v >> 8).astype(np.uint8)
+        host_buf[pos + 1] = v.astype(np.uint8)
+    return ok
 
 
 def make_groups(firsts, counts) -> np.ndarray:
@@ -198,6 +230,23 @@ class ChecksumEngine:
                                          self._stream(stream)), "smol_csum_batch_emit")
         return status
 
+    def emit_fields(self, buf, batch: Batch, caps=None, fields=None, stream=None):
+        """Emit's values without the writes (smol_csum_batch_emit_fields): returns an n x 16 uint8
+        device tensor of smol_csum_fields_t (view its host copy as FIELDS_DTYPE; apply_fields patches
+        host frames with it).  `buf` is only read."""
+        import torch
+
+        self._check_buf(buf, batch)
+        if fields is None:
+            fields = torch.empty((batch.n, 16), dtype=torch.uint8, device=buf.device)
+        assert fields.is_cuda and fields.is_contiguous() and fields.numel() >= 16 * batch.n
+        b = batch.c()
+        c = _caps(caps)
+        check(self._L.smol_csum_batch_emit_fields(self._h, buf.data_ptr(), ctypes.byref(b), ctypes.byref(c),
+                                                fields.data_ptr(), self._stream(stream)),
+              "smol_csum_batch_emit_fields")
+        return fields
+
     def copy_emit(self, buf, batch: Batch, src, copies, caps=None, status=None, stream=None):
         """Fused payload copy + emit (smol_csum_batch_copy_emit): ``copies`` is a device uint8
         tensor of n smol_csum_copy_t (see make_copies), ``src`` the payload source tensor."""
@@ -346,6 +395,11 @@ class ChecksumEngine:
     def set_variant(self, variant: int):
         check(self._L.smol_csum_tool_set_variant(self._h, int(variant)), "smol_csum_tool_set_variant")
 
+    def set_fields_kernel(self, kernel: int):
+        """emit_fields' kernel form: 0 the library's choice, 1 the walk kernel, 2 the transposed walk,
+        3 the descriptor walk (a form that does not serve the batch gives way to the walk kernel)."""
+        check(self._L.smol_csum_tool_set_fields_kernel(self._h, int(kernel)), "smol_csum_tool_set_fields_kernel")
+
     def set_tile(self, records: int):
         check(self._L.smol_csum_tool_set_tile(self._h, int(records)), "smol_csum_tool_set_tile")
 
@@ -369,12 +423,13 @@ class ChecksumEngine:
 
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
-        "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel", "variant": VAR, "G":
+        "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
-                 6: "dwalk_kernel"}
+                 6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

@@ -189,6 +189,17 @@ public:
         check(smol_csum_batch_emit(ctx_, d_buf, &bc, &cc, d_status, stream), "smol_csum_batch_emit");
     }
 
+    // Emit's values without the writes: d_fields[i] = record i's field offsets, values and status
+    // (16-byte aligned device array); d_buf is only read.  The frames stay in host memory and
+    // smol_csum_apply_fields patches them there, two bytes per field as the reference's fill_checksum
+    // (udp.rs:194-208, tcp.rs:616-626, ipv4.rs:506-513).
+    void emit_fields(const uint8_t* d_buf, const Batch& b, smol_csum_fields_t* d_fields,
+                     const smoltcp::phy::ChecksumCapabilities& caps = {}, void* stream = nullptr) {
+        auto bc = b.c();
+        auto cc = caps.c();
+        check(smol_csum_batch_emit_fields(ctx_, d_buf, &bc, &cc, d_fields, stream), "smol_csum_batch_emit_fields");
+    }
+
     // TcpRepr/UdpRepr::emit's "copy the payload, then fill": d_copy[i] moves record i's payload
     // from d_src into the record, then the checksums are emitted, in one pass.
     void copy_emit(uint8_t* d_buf, const Batch& b, const uint8_t* d_src, const smol_csum_copy_t* d_copy,

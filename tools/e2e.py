@@ -7,6 +7,8 @@ three HIP streams, `--buffers` device chunks in rotation (default 2: double-buff
 
     TX:  H2D(frames) -> smol_csum_batch_emit -> D2H(frames with checksums)
     RX:  H2D(frames) -> smol_csum_batch_verify -> D2H(status bytes)
+    TX (fields): H2D(frames) -> smol_csum_batch_emit_fields -> D2H(16 B per frame) -> numpy patch of the
+         host frames (engine.apply_fields), chunk by chunk as each chunk's entries arrive
 
 Reported: record bytes per second through the whole pipeline, next to the bare PCIe copy rates
 measured in the same process.
@@ -47,6 +49,13 @@ def run(n_records: int = 1 << 20, chunk: int = 1 << 17, L: int = 1500, reps: int
     dbuf = [torch.empty(chunk * L, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
     dst = [torch.empty(chunk, dtype=torch.uint8, device=dev) for _ in range(nbuf)]
     s_h2d, s_cmp, s_d2h = (torch.cuda.Stream(dev) for _ in range(3))
+    # emit_fields: a chunk's entries on the device, every record's entry in pinned host memory
+    dfl = [torch.empty((chunk, 16), dtype=torch.uint8, device=dev) for _ in range(nbuf)]
+    host_fl = torch.empty((n_records, 16), dtype=torch.uint8, pin_memory=True)
+    host_np, host_fl_np = host_in.numpy(), host_fl.numpy()
+    import numpy as np
+
+    rec_offs = np.arange(n_records, dtype=np.int64) * L
 
     def pipeline(mode: str):
         e_h2d = [torch.cuda.Event() for _ in range(nchunks)]
@@ -66,6 +75,8 @@ def run(n_records: int = 1 << 20, chunk: int = 1 << 17, L: int = 1500, reps: int
                 b = E.Batch.fixed(m, L, L, E.KIND_IP)
                 if mode == "tx":
                     eng.emit(dbuf[k], b, stream=s_cmp)
+                elif mode == "tx_fields":
+                    eng.emit_fields(dbuf[k], b, fields=dfl[k], stream=s_cmp)
                 else:
                     eng.verify(dbuf[k], b, status=dst[k], stream=s_cmp)
                 e_cmp[c].record(s_cmp)
@@ -73,10 +84,23 @@ def run(n_records: int = 1 << 20, chunk: int = 1 << 17, L: int = 1500, reps: int
                 s_d2h.wait_event(e_cmp[c])
                 if mode == "tx":
                     host_out[lo:hi].copy_(dbuf[k][:m * L], non_blocking=True)
+                elif mode == "tx_fields":
+                    host_fl[c * chunk:c * chunk + m].copy_(dfl[k][:m], non_blocking=True)
                 else:
                     host_st[c * chunk:c * chunk + m].copy_(dst[k][:m], non_blocking=True)
                 e_d2h[c].record(s_d2h)
+            if mode == "tx_fields" and c >= 1:
+                patch(c - 1, e_d2h[c - 1])  # while chunk c is in flight
+        if mode == "tx_fields":
+            patch(nchunks - 1, e_d2h[nchunks - 1])
         torch.cuda.synchronize()
+
+    def patch(c, ev):
+        # chunk c's entries have arrived: the host writes its frames' fields (the frames never left)
+        ev.synchronize()
+        r0, r1 = c * chunk, min((c + 1) * chunk, n_records)
+        ok = E.apply_fields(host_np, rec_offs[r0:r1], L, host_fl_np[r0:r1])
+        assert ok.all()
 
     def timed(fn):
         fn()  # warm-up
@@ -131,6 +155,17 @@ def run(n_records: int = 1 << 20, chunk: int = 1 << 17, L: int = 1500, reps: int
         st = eng.verify(chk, E.Batch.fixed(m, L, L, E.KIND_IP))
         acc += int(((st & E.ST_ACCEPT) != 0).sum())
     res["tx_output_accepted"] = acc
+    # the fields path last: it patches host_in, the frames the other pipelines read with zero fields
+    t_txf = timed(lambda: pipeline("tx_fields"))
+    res["tx_fields_e2e_GBs"] = round(total / t_txf / 1e9, 2)
+    res["tx_fields_over_h2d"] = round(res["tx_fields_e2e_GBs"] / res["h2d_GBs"], 3)
+    acc = 0
+    for c in range(nchunks):
+        m = min(chunk, n_records - c * chunk)
+        chk[:m * L].copy_(host_in[c * chunk * L:(c * chunk + m) * L])
+        st = eng.verify(chk, E.Batch.fixed(m, L, L, E.KIND_IP))
+        acc += int(((st & E.ST_ACCEPT) != 0).sum())
+    res["tx_fields_output_accepted"] = acc
     return res
 
 

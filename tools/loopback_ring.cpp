@@ -10,7 +10,11 @@
 //   CPU inline:  the same fill + verify per frame with the scalar mirrors on one host thread
 //                (what smoltcp does in Ipv4Repr/TcpRepr::emit and ::parse with caps = Both).
 //
-//   loopback_ring [frames] [reps] [dump-prefix]      prints one JSON line
+//   loopback_ring [frames] [reps] [dump-prefix] [fields]      prints one JSON line
+//
+// With `fields` as the 4th argument the GPU TX pass is OffloadRing::emit_fields (H2D ->
+// smol_csum_batch_emit_fields -> D2H of 16 B per frame -> the host writes the fields into the ring), and
+// the JSON line gains "tx_path": "emit_fields".
 //
 // With a dump prefix, every 97th frame of the last GPU pass is written out as built (zero checksum
 // fields: PREFIX.before), after OffloadRing::emit (PREFIX.after) and its verify status byte
@@ -77,6 +81,11 @@ static bool cpu_verify(const uint8_t* f) {
 int main(int argc, char** argv) {
     const uint32_t n = argc > 1 ? uint32_t(std::atoi(argv[1])) : (1u << 18);
     const int reps = argc > 2 ? std::atoi(argv[2]) : 5;
+    const bool fields = argc > 4 && std::strcmp(argv[4], "fields") == 0;
+    if (argc > 4 && !fields) {
+        std::fprintf(stderr, "loopback_ring: unknown 4th argument '%s' (expected: fields)\n", argv[4]);
+        return 2;
+    }
     std::vector<uint8_t> sockbuf(size_t(kMss) * 64);
     for (size_t i = 0; i < sockbuf.size(); ++i) sockbuf[i] = uint8_t(i * 2654435761u >> 24);
     try {
@@ -86,15 +95,19 @@ int main(int argc, char** argv) {
         };
         const double bytes = double(n) * kFrame;
         // ---- GPU offload
+        auto tx = [&] {
+            if (fields) ring.emit_fields(n);
+            else ring.emit(n);
+        };
         build_all();
-        ring.emit(n);  // warm-up (also JIT-free first launch)
+        tx();  // warm-up (also JIT-free first launch)
         ring.verify(n);
         double t_emit = 0, t_verify = 0;
         uint64_t accepted = 0;
         for (int r = 0; r < reps; ++r) {
             build_all();
             auto t0 = Clock::now();
-            ring.emit(n);
+            tx();
             auto t1 = Clock::now();
             ring.verify(n);  // the TX ring looped back as the RX ring
             auto t2 = Clock::now();
@@ -102,7 +115,7 @@ int main(int argc, char** argv) {
             t_verify += std::chrono::duration<double>(t2 - t1).count();
         }
         for (uint32_t i = 0; i < n; ++i) accepted += smoltcp_amd::accepted(ring.status()[i]);
-        if (argc > 3) {  // the sample the oracle checks: frames as built, as emitted, their status
+        if (argc > 3 && argv[3][0]) {  // (an empty prefix: no dump) the sample the oracle checks: frames as built, as emitted, their status
             const std::string pre = argv[3];
             FILE* fb = std::fopen((pre + ".before").c_str(), "wb");
             FILE* fa = std::fopen((pre + ".after").c_str(), "wb");
@@ -139,11 +152,11 @@ int main(int argc, char** argv) {
         }
         std::printf(
             "{\"workload\": \"C1 analogue: %u Ethernet+IPv4+TCP frames of %u B (MSS %u) in a pinned loopback ring\", "
-            "\"frames\": %u, \"frame_bytes\": %u, "
+            "\"frames\": %u, \"frame_bytes\": %u, %s"
             "\"gpu_offload\": {\"emit_GBs\": %.2f, \"verify_GBs\": %.2f, \"roundtrip_GBs\": %.2f, \"accepted\": %llu, "
             "\"host_gate_sample_accepted\": %llu, \"host_gate_sample\": %u}, "
             "\"cpu_inline_1thread\": {\"emit_GBs\": %.2f, \"verify_GBs\": %.2f, \"roundtrip_GBs\": %.2f, \"accepted\": %llu}}\n",
-            n, kFrame, kMss, n, kFrame, bytes * reps / t_emit / 1e9, bytes * reps / t_verify / 1e9,
+            n, kFrame, kMss, n, kFrame, fields ? "\"tx_path\": \"emit_fields\", " : "", bytes * reps / t_emit / 1e9, bytes * reps / t_verify / 1e9,
             bytes * reps / (t_emit + t_verify) / 1e9, (unsigned long long)accepted, (unsigned long long)cross,
             (n + 96) / 97, bytes * creps / c_emit / 1e9, bytes * creps / c_verify / 1e9,
             bytes * creps / (c_emit + c_verify) / 1e9, (unsigned long long)c_acc);
