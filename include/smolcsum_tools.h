@@ -156,6 +156,12 @@ int smol_csum_tool_variant_info(int variant, int out[4]);
  * (the rest 0).  Read through the switch the launchers instantiate their kernels with.  SMOL_EINVAL: not
  * such a variant, or it has no form of that op. */
 int smol_csum_tool_form(int variant, int op, int out[13]);
+/* The walk kernel (csum_kernel) that a launch of `variant` would run for `op` (0 data, 1 emit, 2 verify,
+ * 3 copy-emit) over a fixed-stride (`implicit` != 0) or descriptor batch, a 6LoWPAN NHC batch when `nhc`,
+ * at launch shape `shape` (0-8): out = {kernel id (1 walk, 4 NHC walk), the variant reported to
+ * smol_csum_tool_last_launch, G, U}.  Read from the switch and the shape mapper the launcher runs; it
+ * launches nothing.  SMOL_EINVAL: the walk kernel has no launch for it in this library. */
+int smol_csum_tool_walk_launch(int variant, int op, int implicit, int nhc, int shape, int out[4]);
 
 /* The kernel (the rocprofv3 name prefix: "csum_kernel", "csum_tile_kernel", "xwalk_kernel",
  * "dwalk_kernel", "copy_kernel" or "xcopy_kernel") that an IP-path operation on `batch` runs with this
@@ -171,8 +177,8 @@ const char* smol_csum_tool_kernel_name(const smol_csum_ctx_t* ctx, int op, int h
 /* The kernel instantiation of this process's last checksum launch (any context), packed as
  * kernel << 24 | variant << 16 | G << 8 | U; kernel 1 = csum_kernel, 2 = csum_tile_kernel,
  * 3 = copy_kernel, 4 = csum_kernel with the 6LoWPAN NHC gates, 5 = xwalk_kernel, 6 = dwalk_kernel;
- * smol_csum_batch_emit_fields (variant 0): 7 = csum_fields_kernel, 8 = xwalk_kernel with the fields sink,
- * 9 = dwalk_kernel with it; 0 before the first launch. */
+ * smol_csum_batch_emit_fields (variant 0): 7 = csum_kernel with the fields sink (the tools label it
+ * "csum_fields_kernel"), 8 = xwalk_kernel with it, 9 = dwalk_kernel with it; 0 before the first launch. */
 uint32_t smol_csum_tool_last_launch(void);
 
 /* 1 when this build of the library runs kernel variant `variant` (smol_csum_tool_set_variant), else

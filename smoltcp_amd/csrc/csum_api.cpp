@@ -708,6 +708,36 @@ int smol_csum_tool_form(int variant, int op, int out[13]) {
     return d && !none ? SMOL_OK : SMOL_EINVAL;
 }
 
+int smol_csum_tool_walk_launch(int variant, int op, int implicit, int nhc, int shape, int out[4]) {
+    if (!out || op < MODE_DATA || op > MODE_COPY || shape < 0 || shape >= CFG_COUNT) return SMOL_EINVAL;
+    if (nhc && op != MODE_EMIT && op != MODE_VERIFY) return SMOL_EINVAL;
+    const int kern = nhc ? KERN_WALK_NHC : KERN_WALK;
+    auto note = [&](auto, auto num, auto g, auto u) {
+        const int v[4] = {kern, decltype(num)::value, decltype(g)::value, decltype(u)::value};
+        std::memcpy(out, v, sizeof v);
+    };
+    auto batch_form = [&](auto mode, auto is_nhc) {
+        constexpr int MODE = decltype(mode)::value;
+        constexpr bool NHC = decltype(is_nhc)::value;
+        return implicit ? with_walk_kernel<MODE, true, NHC>(variant, shape, note)
+                        : with_walk_kernel<MODE, false, NHC>(variant, shape, note);
+    };
+    using std::integral_constant;
+    bool ok = false;
+    if (nhc) {
+        ok = op == MODE_EMIT ? batch_form(integral_constant<int, MODE_EMIT>{}, std::true_type{})
+                             : batch_form(integral_constant<int, MODE_VERIFY>{}, std::true_type{});
+    } else {
+        switch (op) {
+            case MODE_DATA: ok = batch_form(integral_constant<int, MODE_DATA>{}, std::false_type{}); break;
+            case MODE_EMIT: ok = batch_form(integral_constant<int, MODE_EMIT>{}, std::false_type{}); break;
+            case MODE_VERIFY: ok = batch_form(integral_constant<int, MODE_VERIFY>{}, std::false_type{}); break;
+            default: ok = batch_form(integral_constant<int, MODE_COPY>{}, std::false_type{}); break;
+        }
+    }
+    return ok ? SMOL_OK : SMOL_EINVAL;
+}
+
 uint32_t smol_csum_tool_last_launch(void) { return g_last_launch.load(std::memory_order_relaxed); }
 
 }  // extern "C"

@@ -8,10 +8,12 @@
 #include <atomic>
 
 #include "../../include/smolcsum.h"
+#include "csum_variants.h"
 
 namespace smolcsum {
 
 enum { MODE_DATA = 0, MODE_EMIT = 1, MODE_VERIFY = 2, MODE_COPY = 3 };  // COPY: fused copy + emit
+static_assert(MODE_DATA == kOpData && MODE_EMIT == kOpEmit && MODE_VERIFY == kOpVerify && MODE_COPY == kOpCopy, "csum_variants.h");
 
 // Internal record kind of the 6LoWPAN NHC UDP entry points (never in a descriptor).
 constexpr uint32_t KIND_NHC_UDP = 0x10;
@@ -35,6 +37,88 @@ enum {
     CFG_G16U4 = 8,
     CFG_COUNT = 9
 };
+
+// The walk kernel's shape sets (csum_variants.h WalkShapes): fn(G, U) on the shape of SET that `shape`
+// (a CFG_*) maps to.  A kernel is instantiated for the shapes of its set only.
+#define WALK_SHAPE(g, u) return (void)fn(std::integral_constant<int, g>{}, std::integral_constant<int, u>{})
+template <int SET, class Fn>
+inline void with_walk_shape(int shape, Fn&& fn) {
+    if constexpr (SET == S_ALL9) {  // every shape its own
+        switch (shape) {
+            case CFG_G8U6: WALK_SHAPE(8, 6);
+            case CFG_G8U7: WALK_SHAPE(8, 7);
+            case CFG_G16U3: WALK_SHAPE(16, 3);
+            case CFG_G16U4: WALK_SHAPE(16, 4);
+            case CFG_G16U6: WALK_SHAPE(16, 6);
+            case CFG_G32U3: WALK_SHAPE(32, 3);
+            case CFG_G32U4: WALK_SHAPE(32, 4);
+            case CFG_G64U2: WALK_SHAPE(64, 2);
+            default: WALK_SHAPE(64, 4);
+        }
+    } else if constexpr (SET == S_SEG6) {
+        // the whole-segment emit walks: the shapes emit picks (8 x 6 / 8 x 7 at a fixed stride, 16 x 3 /
+        // 16 x 4 over descriptors) and 32 x 4 / 64 x 4 for long records; the others map to the one with
+        // the same group size
+        switch (shape) {
+            case CFG_G8U6: WALK_SHAPE(8, 6);
+            case CFG_G8U7: WALK_SHAPE(8, 7);
+            case CFG_G16U3: WALK_SHAPE(16, 3);
+            case CFG_G16U4:
+            case CFG_G16U6: WALK_SHAPE(16, 4);
+            case CFG_G32U3:
+            case CFG_G32U4: WALK_SHAPE(32, 4);
+            default: WALK_SHAPE(64, 4);
+        }
+    } else if constexpr (SET == S_EXP2) {  // fixed-stride emit experiments: 8 x 6, every other shape 8 x 7
+        if (shape == CFG_G8U6) WALK_SHAPE(8, 6);
+        WALK_SHAPE(8, 7);
+    } else if constexpr (SET == S_COPY4) {
+        // MODE_COPY keeps three chunks per lane and step (record + two source chunks): the U <= 3 shapes,
+        // wider ones map to the same group size with fewer chunks
+        switch (shape) {
+            case CFG_G8U6:
+            case CFG_G8U7: WALK_SHAPE(8, 3);
+            case CFG_G32U3:
+            case CFG_G32U4: WALK_SHAPE(32, 3);
+            case CFG_G64U2:
+            case CFG_G64U4: WALK_SHAPE(64, 2);
+            default: WALK_SHAPE(16, 3);
+        }
+    } else if constexpr (SET == S_NHC3) {  // 6LoWPAN NHC: 8 x 6, 8 x 7, every other shape 16 x 3
+        if (shape == CFG_G8U6) WALK_SHAPE(8, 6);
+        if (shape == CFG_G8U7) WALK_SHAPE(8, 7);
+        WALK_SHAPE(16, 3);
+    } else if constexpr (SET == S_FIXED5) {  // emit_fields: the shapes auto_shape gives 5 over fixed strides
+        switch (shape) {
+            case CFG_G8U6: WALK_SHAPE(8, 6);
+            case CFG_G8U7: WALK_SHAPE(8, 7);
+            case CFG_G16U6: WALK_SHAPE(16, 6);
+            case CFG_G32U4: WALK_SHAPE(32, 4);
+            default: WALK_SHAPE(64, 4);
+        }
+    } else {  // S_G16U3, emit_fields over descriptors: 16 x 3 whatever the shape
+        static_assert(SET == S_G16U3, "shape set");
+        WALK_SHAPE(16, 3);
+    }
+}
+#undef WALK_SHAPE
+
+// The walk kernel a call runs: fn(form, number reported, G, U), from the registry's switch and the shape
+// mappers; false: none (an error).  launch_walk and launch_walk_nhc (csum_walk.h) launch
+// through it and smol_csum_tool_walk_launch reads it.
+template <int MODE, bool IMPLICIT, bool NHC, class Fn>
+inline bool with_walk_kernel(int variant, int shape, Fn&& fn) {
+    auto shaped = [&](auto form, auto num, auto set) {
+        with_walk_shape<decltype(set)::value>(shape, [&](auto g, auto u) { fn(form, num, g, u); });
+    };
+    if constexpr (NHC) {
+        static_assert(MODE == MODE_EMIT || MODE == MODE_VERIFY, "the NHC entry points");
+        with_walk_nhc_form(variant, shaped);
+        return true;
+    } else {
+        return with_walk_form<MODE, IMPLICIT>(variant, shaped);
+    }
+}
 
 struct KParams {
     uint8_t* buf;
@@ -114,7 +198,8 @@ __host__ __device__ inline uint32_t grid_blocks(uint64_t want, uint64_t cap) {
 uint32_t resident_blocks(const void* kernel, uint32_t num_cu, uint32_t max_blocks);
 
 hipError_t launch_csum(int mode, int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s);
-// Walk kernel for one (mode, batch form): csum_walk.h, instantiated in csum_walk_*.hip.
+// Walk kernel for one (mode, batch form): csum_walk.h, instantiated in csum_walk_*.hip (MODE_COPY: the
+// experiments build's csum_walk_copy.hip).
 template <int MODE, bool IMPLICIT>
 hipError_t launch_walk(int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s);
 // The same for 6LoWPAN NHC UDP batches (p.addrs set), csum_walk_nhc.hip.

@@ -1,14 +1,91 @@
-// Reader of variants.def: the variant table and its lookups, the named forms of xwalk_kernel and
-// dwalk_kernel, and the switches from (variant, mode) to a form.  Host-only (no HIP): csum_dispatch.h,
+// Reader of variants.def: the variant table and its lookups, the named forms of csum_kernel, xwalk_kernel
+// and dwalk_kernel, and the switches from (variant, mode) to a form.  Host-only (no HIP): csum_dispatch.h,
 // the launchers and the tooling entry points all read variants through this file.
 #pragma once
 
 #include <stdint.h>
 
+#include <type_traits>
+
 namespace smolcsum {
 
 enum Family { F_WALK, F_TILE, F_XWALK, F_DWALK, F_STRIPE, F_COPY, F_XCOPY };
 enum VariantFlags { V_COPY_ONLY = 1, V_WALK_COPY = 2, V_LINE = 4, V_G16U4 = 8, V_STAGED = 16, V_NOSTORE = 32, V_NHC_LINE = 64 };
+
+// ---- csum_kernel's forms (the walk kernel, csum_walk.h) ---------------------------------------------
+// The defaults are the plainest walk: the 16-B chunk grid, loads with the default cache policy, the next
+// step prefetched into a second register set.  csum_walk.h's WalkTraits gates the emit-only members by
+// mode and batch form; the measurements behind each form are in DESIGN.md §5 / §6.
+struct WPlain {
+    static constexpr bool NT = false;     // non-temporal loads
+    static constexpr bool PF = true;      // register prefetch of the next step
+    static constexpr bool LINE = false;   // chunk grid from the record's 128-B line (nt loads need whole lines)
+    static constexpr int CACHED_U = 0;    // the first CACHED_U chunks of every lane's step loaded cached
+    static constexpr int CU0 = 0;         // ... of a group's first load only (0: CACHED_U)
+    // copy-emit (MODE_COPY): the second source chunk from the next lane; dword-aligned source loads; every
+    // byte of the record written
+    static constexpr bool SHUF = false, SHUF2 = false, WHOLE = false;
+    // fixed-stride emit: whole 64-B field segments, the neighbours' field ranges published in LDS (SEGW);
+    // SEGOPT bit 0: skipped on wavefronts that hold no IPv4 record
+    static constexpr bool SEGW = false;
+    static constexpr int SEGOPT = 0;
+    // emit: the same with the neighbours' record extents published, so descriptor batches too (SEGG); the
+    // whole workgroup's neighbours (SEGB); IPv6 records too (SEG6)
+    static constexpr bool SEGG = false, SEGB = false, SEG6 = false;
+    // fixed-stride emit: whole segments decided by one ballot (BSEG); IPv6 records too (BSEG6); only on
+    // wavefronts without an IPv4 record (BSEG_NO4); the segments stored write-through non-temporal (NTSEG)
+    static constexpr bool BSEG = false, BSEG6 = false, BSEG_NO4 = false, NTSEG = false;
+    static constexpr bool GLDS = false;     // emit: the record geometry in LDS (as verify keeps it)
+    static constexpr bool NOSHARE = false;  // fixed-stride emit: no shared boundary lines (shared_from)
+    static constexpr bool NOSTORE = false;  // emit: every store compiled out (wrong bytes, timing only)
+    static constexpr int MIN_WAVES = 1;     // occupancy floor, wavefronts per SIMD
+    static constexpr bool FIELDS = false;   // emit: the fields sink (WFields)
+};
+enum WalkOpt { WO_GLDS = 1, WO_NOSHARE = 2, WO_BLOCK = 4, WO_IPV6 = 8 };
+struct WNt : WPlain { static constexpr bool NT = true; };         // 0
+struct WNtNoPf : WNt { static constexpr bool PF = false; };       // 2
+struct WNoPf : WPlain { static constexpr bool PF = false; };      // 8: fewer VGPRs, more waves: C2 copy-emit 0.95 -> 0.85 ms
+struct WShuf : WNoPf { static constexpr bool SHUF = true; };      // 11
+struct WShufDword : WShuf { static constexpr bool SHUF2 = true, WHOLE = true; };  // 16: four v_alignbyte, one dword from the next lane
+struct WLinePlain : WPlain { static constexpr bool LINE = true; };  // 6
+struct WLine : WLinePlain { static constexpr bool NT = true; };     // 5: 16-B grid + nt 5.8 TB/s, line grid + nt 7.3 TB/s
+template <int N> struct WLineCached : WLine { static constexpr int CACHED_U = N; };  // 9, 10: the fields' lines stay in L2 for the field stores
+struct WLineNoPf : WLine { static constexpr bool PF = false; };         // 13
+struct WLineNoStore : WLine { static constexpr bool NOSTORE = true; };  // 69
+// emit_fields (smol_csum_batch_emit_fields): 5's emit walk, every record's 16-B entry to p.fields instead of
+// its fields into the record.  No variants.def row: launch_walk_fields runs it, outside the registry.
+struct WFields : WLine { static constexpr bool FIELDS = true; };
+template <int O> struct WLineExp : WLine {  // 31, 35, 36: emit walks shaped like verify's
+    static constexpr bool GLDS = (O & WO_GLDS) != 0, NOSHARE = (O & WO_NOSHARE) != 0;
+};
+struct WSeg19 : WLine { static constexpr bool SEGW = true; };    // 19: C2 emit 0.305 -> 0.285 ms when every segment goes out whole
+// 29: IPv6 records have one field and keep the 2-B store (round 4 also measured its segments stored
+// non-temporal: C2 emit 0.303 against 0.296 ms; removed)
+struct WSeg29 : WSeg19 { static constexpr int SEGOPT = 1; };
+template <int O> struct WSeg29Exp : WSeg29 {  // 32, 33, 34
+    static constexpr bool GLDS = (O & WO_GLDS) != 0, NOSHARE = (O & WO_NOSHARE) != 0;
+};
+template <int O> struct WBallot : WLine {  // 37, 38
+    static constexpr bool BSEG = true, BSEG6 = (O & WO_IPV6) != 0;
+};
+struct WSeg39 : WSeg29 { static constexpr bool BSEG = true, BSEG6 = true, BSEG_NO4 = true; };  // 39: 29 with an IPv4 record, 38's ballot without
+struct WSeg39NtSeg : WSeg39 { static constexpr bool NTSEG = true; };    // 40: plain nt lost (round 5); now sc1 nt as xwalk's 101
+struct WSeg39CachedFirst : WSeg39 { static constexpr int CU0 = 2; };    // 12: the header lines (the LDS window) cached, so the field stores hit L2
+struct WSeg39CachedEvery : WSeg39 { static constexpr int CACHED_U = 2; };  // 14
+template <int O> struct WSegG : WLine {  // 23, 24, 25
+    static constexpr bool SEGG = true, SEGB = (O & WO_BLOCK) != 0, SEG6 = (O & WO_IPV6) != 0;
+};
+template <int O> struct WSegGNoPf : WSegG<O | WO_IPV6> { static constexpr bool PF = false; };  // 26, 27
+struct WSegG28 : WSegGNoPf<0> { static constexpr int MIN_WAVES = 7; };  // 28: 13's occupancy at 16 x 4; the segment decision otherwise costs two waves
+
+// Where a WALK row's own kernel runs (smol_csum_batch_data / emit / verify; elsewhere the row's `else`
+// number runs and is the one reported, or the call is an error).  Copy-emit is apart: the walk kernel's
+// MODE_COPY form of a number runs exactly where the row has V_WALK_COPY, on copy's shapes.
+enum WalkScope { W_ALL, W_EMIT, W_EMIT_FIXED, W_COPY };
+constexpr int W_ERR = -2;  // `else`: no kernel (hipErrorInvalidValue)
+// The shapes a kernel is built for (csum_launch.h with_walk_shape maps every CFG_* into the set).
+enum WalkShapes { S_ALL9, S_SEG6, S_EXP2, S_COPY4, S_NHC3, S_FIXED5, S_G16U3 };
+constexpr int kOpData = 0, kOpEmit = 1, kOpVerify = 2, kOpCopy = 3;  // csum_launch.h MODE_*
 
 // ---- xwalk_kernel's forms (csum_xwalk.hip explains each constant) -----------------------------------
 enum XwalkNts {
@@ -133,7 +210,7 @@ struct Variant {
 #define V_BUILD_P false
 #define V_BUILD_X true
 inline constexpr Variant kVariants[] = {
-#define WALK(n, b, fl, ft, d) {n, F_WALK, V_BUILD_##b, fl, ft, SELF, 0, true, true, d},
+#define WALK(n, b, fl, ft, form, scope, els, shapes, d) {n, F_WALK, V_BUILD_##b, fl, ft, SELF, 0, true, true, d},
 #define TILE(n, b, loads, d) {n, F_TILE, V_BUILD_##b, 0, SELF, SELF, loads, true, true, d},
 #define STRIPE(n, b, d) {n, F_STRIPE, V_BUILD_##b, 0, SELF, SELF, 0, true, true, d},
 #define COPY(n, b, d) {n, F_COPY, V_BUILD_##b, V_COPY_ONLY, SELF, SELF, 0, false, false, d},
@@ -173,6 +250,70 @@ inline int verify_variant(int v) {
     return r && r->verify_twin != SELF ? r->verify_twin : v;
 }
 
+// ---- the walk kernel's rows -------------------------------------------------------------------------
+template <int N> struct WalkRow;  // the WALK row of number N
+#define WALK(n, b, fl, ft, form, scope, els, shapes, d)                               \
+    template <> struct WalkRow<n> {                                                   \
+        using Form = form;                                                            \
+        static constexpr int FLAGS = fl, SCOPE = scope, ELSE = els, SHAPES = shapes;  \
+    };
+#define TILE(n, b, loads, d)
+#define STRIPE(n, b, d)
+#define COPY(n, b, d)
+#define XCOPY(n, b, d)
+#define XWALK(n, b, fl, ft, ef, vf, d)
+#define DWALK(n, b, fl, ft, vt, ef, vf, d)
+#include "variants.def"
+#undef WALK
+
+// Row N asked for (mode, batch form): fn(form, number reported, shape set) on the row's own kernel where it
+// runs, else on the row's `else` number; false: an error.
+template <int N, int MODE, bool IMPLICIT, class Fn>
+inline bool with_walk_row(Fn&& fn) {
+    using R = WalkRow<N>;
+    constexpr bool own = MODE == kOpCopy ? (R::FLAGS & V_WALK_COPY) != 0
+                         : R::SCOPE == W_ALL || (R::SCOPE == W_EMIT && MODE == kOpEmit) ||
+                               (R::SCOPE == W_EMIT_FIXED && MODE == kOpEmit && IMPLICIT);
+    if constexpr (own) {
+        fn(typename R::Form{}, std::integral_constant<int, N>{},
+           std::integral_constant<int, MODE == kOpCopy ? (int)S_COPY4 : R::SHAPES>{});
+        return true;
+    } else if constexpr (MODE != kOpCopy && R::ELSE >= 0) {
+        return with_walk_row<R::ELSE, MODE, IMPLICIT>(fn);
+    } else {
+        return false;
+    }
+}
+
+// (variant, mode, batch form) -> the walk kernel to run, over the rows built in this library.
+template <int MODE, bool IMPLICIT, class Fn>
+inline bool with_walk_form(int variant, Fn&& fn) {
+    switch (variant) {
+#define V_WALK_P(n) case n: return with_walk_row<n, MODE, IMPLICIT>(fn);
+#ifdef SMOL_EXP
+#define V_WALK_X(n) V_WALK_P(n)
+#else
+#define V_WALK_X(n)
+#endif
+#define WALK(n, b, fl, ft, form, scope, els, shapes, d) V_WALK_##b(n)
+#include "variants.def"
+#undef WALK
+#undef V_WALK_P
+#undef V_WALK_X
+        default: return false;
+    }
+}
+#undef XWALK
+#undef DWALK
+
+// 6LoWPAN NHC batches, any number: the NHC kernel's line-grid form (row 5) for a V_NHC_LINE number, its
+// 16-B-grid form (row 1: an experiments row, but this form of it is built in both libraries) otherwise.
+template <class Fn>
+inline void with_walk_nhc_form(int variant, Fn&& fn) {
+    if (variant_is(variant, V_NHC_LINE)) fn(WalkRow<5>::Form{}, std::integral_constant<int, 5>{}, std::integral_constant<int, S_NHC3>{});
+    else fn(WalkRow<1>::Form{}, std::integral_constant<int, 1>{}, std::integral_constant<int, S_NHC3>{});
+}
+
 // (variant, mode) -> form: calls fn(Form{}) for the row's emit (EMIT) or verify form, over the rows built
 // in this library; false: no such row.  The launchers instantiate kernels through these switches and
 // smol_csum_tool_form reads the same ones.
@@ -186,11 +327,7 @@ inline int verify_variant(int v) {
 #else
 #define V_FORM_X(n, ef, vf)
 #endif
-#define WALK(n, b, fl, ft, d)
-#define TILE(n, b, loads, d)
-#define STRIPE(n, b, d)
-#define COPY(n, b, d)
-#define XCOPY(n, b, d)
+#define WALK(n, b, fl, ft, form, scope, els, shapes, d)
 
 template <bool EMIT, class Fn>
 inline bool with_xwalk_form(int variant, Fn&& fn) {

@@ -45,71 +45,36 @@
 
 namespace smolcsum {
 
-// Kernel variants: load cache policy, register prefetch, chunk-grid alignment.
-// 0 = nt + prefetch, 1 = plain + prefetch, 2 = nt without prefetch, 8 = plain without prefetch
-// (16-byte grid); 5 = nt + prefetch, 6 = plain + prefetch (128-byte line grid).  3 / 4 / 7 are the
-// tile kernel.
-// 9 / 10 = variant 5 with the first two / the first chunk of every lane's step loaded cached
-// (fixed-stride emit only: the 128-B line(s) holding the two fields stay resident in L2 when the
-// field stores arrive; measured in DESIGN.md §5).
-// 13 = variant 5 without the register prefetch.
-// MODE_COPY (16-byte grid, plain loads, no register prefetch): 8 = two aligned source chunks per
-// destination chunk; 11 = one, the second taken from the next lane of the group (DPP /
-// ds_bpermute); 16 (the default) = variant 11 with dword-aligned source loads — a lane loads the 16
-// source bytes from its chunk's first source byte rounded down to 4 (an unaligned 16-byte load), so
-// the funnel is four v_alignbyte and only ONE dword comes from the next lane — and every byte of
-// the record written (WHOLE, see walk_step).  Measured variants that lost are in DESIGN.md §6.
-// Experiment variants (the experiments build, SMOL_EXP, only): emit walks shaped like verify's.
-// 31 = 5 with the geometry in LDS and no shared_from; 32 = 29 with both; 33 = 29 with the geometry
-// in LDS; 34 = 29 without shared_from; 35 = 5 without shared_from; 36 = 5 with the geometry in LDS.
-// VAR | 64 (experiments): the same kernel with every global store of emit compiled out (the values
-// computed and kept live, nothing written; wrong bytes, timing only).  Round 6 reused most numbers from
-// 64 up for other kernels: of these only 64 + 5 is still the walk kernel's (variants.def has every row).
-template <int VAR_>
-struct VarT {
-    static constexpr int VAR = VAR_ & 63;
-    static constexpr bool NOSTORE = (VAR_ & 64) != 0;
-    static constexpr bool GLDS = VAR == 31 || VAR == 32 || VAR == 33 || VAR == 36;
-    // 37 / 38: variant 5 with whole field segments decided by one ballot (BSEG; 38 also IPv6 records)
-    // 39: variant 29 on a wavefront that holds an IPv4 record, 38's ballot decision on one that holds
-    // none (BSEG_NO4: IPv6 records get whole segments too)
-    // 12 / 14 (experiments build): 39 with the header lines (chunks u < 2 of a step: the LDS window)
-    // loaded with the default cache policy, at a group's first load only (12) or at every step (14),
-    // so that the field stores hit lines the L2 holds
-    static constexpr bool BSEG = VAR == 37 || VAR == 38 || VAR == 39 || VAR == 40 || VAR == 12 || VAR == 14;
-    static constexpr bool BSEG6 = VAR == 38 || VAR == 39 || VAR == 40 || VAR == 12 || VAR == 14;
-    static constexpr bool BSEG_NO4 = VAR == 39 || VAR == 40 || VAR == 12 || VAR == 14;
-    static constexpr int CU0 = VAR == 12 ? 2 : 0;
-    // 40 (experiments build): 39 with the whole segments stored non-temporal (round 5: plain nt, lost;
-    // since late round 6 write-through, sc1 nt, as the transposed walk's variant 101)
-    static constexpr bool NTSEG = VAR == 40;
-    static constexpr bool NOSHARE = VAR == 31 || VAR == 32 || VAR == 34 || VAR == 35;
-    static constexpr int BASE = (VAR == 31 || VAR == 35 || VAR == 36 || VAR == 37 || VAR == 38) ? 5
-                                : ((VAR >= 32 && VAR <= 34) || VAR == 39 || VAR == 40 || VAR == 12 || VAR == 14) ? 29 : VAR;
-    static constexpr bool NT = VAR == 0 || VAR == 2 || VAR == 5 || VAR == 9 || VAR == 10 || VAR == 13 || VAR == 19 ||
-                               (VAR >= 23 && VAR <= 29) || (VAR >= 31 && VAR <= 40) || VAR == 12 || VAR == 14;
-    static constexpr bool PF = VAR != 2 && VAR != 8 && VAR != 11 && VAR != 13 && VAR != 16 && VAR != 26 && VAR != 27 &&
-                               VAR != 28;
-    static constexpr bool LINE = VAR == 5 || VAR == 6 || VAR == 9 || VAR == 10 || VAR == 13 || VAR == 19 ||
-                                 (VAR >= 23 && VAR <= 29) || (VAR >= 31 && VAR <= 40) || VAR == 12 || VAR == 14;
-    static constexpr int CACHED_U = (VAR == 9 || VAR == 14) ? 2 : VAR == 10 ? 1 : 0;
-    static constexpr bool SHUF = VAR == 11 || VAR == 16;
-    static constexpr bool WHOLE = VAR == 16;
-    static constexpr bool SHUF2 = VAR == 16;
-    static constexpr bool SEGW = VAR == 19 || BASE == 29;  // variant 5 + whole 64-B field segments (fixed-stride emit, walk_step)
-    // SEGOPT bit 0 (29): the segment machinery skipped on wavefronts that hold no IPv4 record (a
-    // ballot after the parse: IPv6 records have one field and keep the 2-B store).  (Round 4 also
-    // measured the segments stored non-temporal: C2 emit 0.303 against 0.296 ms; removed.)
-    static constexpr int SEGOPT = BASE == 29 ? 1 : 0;
-    // 23-27 (emit): whole 64-B field segments with the neighbours' record extents published too, so
-    // that they serve descriptor batches as well as fixed strides (SEGG); SEGB: the neighbours of the
-    // whole workgroup, not only of the wavefront (a workgroup barrier after the parse, natural grid);
-    // SEG6: IPv6 records too.  23 = 5 + SEGG + SEGB + SEG6, 24 = 23 without SEGB, 25 = 23 without
-    // SEG6, 26 = 13 (no prefetch) + SEGG + SEGB + SEG6, 27 = 26 without SEGB, 28 = 27 compiled for
-    // variant 13's occupancy (MinWaves).
-    static constexpr bool SEGG = VAR >= 23 && VAR <= 28;
-    static constexpr bool SEGB = VAR == 23 || VAR == 25 || VAR == 26;
-    static constexpr bool SEG6 = VAR == 23 || VAR == 24 || VAR == 26 || VAR == 27 || VAR == 28;
+// What varies between the kernels of this family is a FORM (csum_variants.h: WPlain and the structs that
+// override it): the load cache policy, the register prefetch, the chunk-grid alignment, copy-emit's source
+// funnel, and emit's ways of writing whole 64-B field segments.  variants.def says which number runs
+// which form where.  A kernel reads its form through WalkTraits, which adds the mode and batch form and
+// gates the emit-only members by them once; nothing else in this file decides what a member means here.
+template <class Form, int MODE_, bool IMPLICIT_, bool NHC_>
+struct WalkTraits : Form {
+    static constexpr int MODE = MODE_;
+    static constexpr bool IMPLICIT = IMPLICIT_, NHC = NHC_;
+    static constexpr bool COPY = MODE == MODE_COPY;
+    static constexpr bool EMIT_LINE = MODE == MODE_EMIT && Form::LINE && !NHC;  // where whole segments exist
+    static constexpr bool SEGW = Form::SEGW && EMIT_LINE && IMPLICIT;
+    static constexpr bool SEGG = Form::SEGG && EMIT_LINE;
+    static constexpr bool SEGB = SEGG && Form::SEGB;
+    static constexpr bool SEG6 = SEGG && Form::SEG6;
+    static constexpr bool BSEG = Form::BSEG && EMIT_LINE && IMPLICIT;
+    static constexpr bool SEGF = SEGW || BSEG;  // the finish writes the segments decided after the parse
+    // where the record geometry lives (Walk::g / Walk::gr): registers for emit with the register
+    // prefetch, LDS otherwise
+    static constexpr bool GREG = MODE == MODE_EMIT && Form::PF && !Form::GLDS;
+    // Fixed-stride batches: no prefetch once the group has nothing left (one record per group in
+    // a natural grid), measured 1-1.5 % faster (C2 verify 0.2444 -> 0.2422 ms, C4 0.2219 -> 0.2189
+    // ms).  Descriptor batches keep the unconditional prefetch: there the conditional load made
+    // C3 verify 25 % slower (0.810 -> 0.989 ms).
+    static constexpr bool SKIPD = IMPLICIT;
+    // csum_kernel has two loops.  The prefetching one was never built with SHUF2 / WHOLE; the plain one
+    // loads every chunk with the form's policy and has no LDS-published or ballot segments.  A form that
+    // asks for another combination asks for a kernel that does not exist.
+    static_assert(!Form::PF || (!Form::SHUF2 && !Form::WHOLE), "SHUF2 / WHOLE: forms without the prefetch");
+    static_assert(Form::PF || (Form::CACHED_U == 0 && Form::CU0 == 0 && !Form::SEGW && !Form::BSEG), "prefetching forms only");
 };
 
 template <bool LINE>
@@ -211,10 +176,13 @@ struct Regs<U, true> {
 // [A, A + 16) lies inside the source range's aligned chunks [first, last + 16); otherwise (the
 // payload's first / last chunk) at first / last, and the merge shifts it there.  Lane 0 also loads
 // the dword at A of the chunk after the step (sx1), for the group's last lane.
-template <int G, int U, bool NT, bool COPY, bool LINE, int CACHED_U = 0, bool SHUF = false, bool SHUF2 = false>
-__device__ __forceinline__ void load_step(Regs<U, COPY>& R, const RecRef& rr, uint32_t nch,
+// T: the kernel's WalkTraits; CACHED_U: the chunks of this load taken with the default cache policy (the
+// form's CACHED_U, or its CU0 at a group's first load).
+template <int G, int U, class T, int CACHED_U>
+__device__ __forceinline__ void load_step(Regs<U, T::COPY>& R, const RecRef& rr, uint32_t nch,
                                           uint32_t step, int lane, bool valid, uint64_t dummy,
                                           uint64_t lim = ~0ull) {
+    constexpr bool NT = T::NT, COPY = T::COPY, LINE = T::LINE, SHUF = T::SHUF, SHUF2 = T::SHUF2;
     static_assert(!(COPY && LINE), "MODE_COPY uses the 16-byte grid");
     const uint64_t base = rr.a0 & ~(Grid<LINE>::ALIGN - 1);
     if constexpr (COPY && SHUF2) {
@@ -374,6 +342,18 @@ __device__ __forceinline__ void store_be16(gu8 q, uint32_t v) {
     }
 }
 
+// Store the bytes of dword v that the byte mask keep selects: a dword store where the whole dword goes
+// out, byte stores otherwise.
+__device__ __forceinline__ void store_dword_masked(gu8 dst, uint32_t v, uint32_t keep) {
+    if (keep == 0xffffffffu) {
+        *(GMEM uint32_t*)dst = v;
+    } else if (keep) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            if (keep & (0xffu << (8 * j))) dst[j] = (uint8_t)(v >> (8 * j));
+    }
+}
+
 // Sum of the chunk's bytes inside [lo, hi) (chunk-relative byte positions), as aligned u16 words.
 __device__ __forceinline__ uint32_t sum_masked_words(const u32x4& c, int lo, int hi, uint32_t acc) {
     acc = add_words(mask_dword(c.x, lo, hi), acc);
@@ -430,6 +410,18 @@ __device__ __forceinline__ void emit_fields(const Geom& g, uint32_t f[3]) {
     f[0] = g.fam == 4 ? g.ip_off + 10 : NO_FIELD;
     f[1] = (g.proto != P_NONE && !(g.st & SMOL_ST_MALFORMED)) ? g.l4_off + g.fo : NO_FIELD;
     f[2] = g.in_off ? g.in_off + 10 : NO_FIELD;
+}
+// ... and the record-offset range [lo, hi) they span (lo = NO_FIELD, hi = 0: none).
+__device__ __forceinline__ void field_range(const Geom& g, uint32_t& lo, uint32_t& hi) {
+    uint32_t f[3];
+    lo = NO_FIELD;
+    hi = 0;
+    emit_fields(g, f);
+    for (int j = 0; j < 3; ++j)
+        if (f[j] != NO_FIELD) {
+            lo = f[j] < lo ? f[j] : lo;
+            hi = f[j] + 2 > hi ? f[j] + 2 : hi;
+        }
 }
 
 // Staged emit (round 6; csum_dwalk.hip variants 94-97, csum_xwalk.hip variants 80 / 81): a record whose
@@ -691,9 +683,9 @@ __device__ __forceinline__ void finish_gates(const KParams& p, const Geom& g, ui
 // window is used only when record r+1 is the neighbour's one and only record (the natural grid),
 // so that it is filled at the start and never overwritten.  Stride >= 384 keeps that line out of
 // record r's own window.
-template <int G, int MODE, bool IMPLICIT, bool LINE, bool NOSHARE = false>
+template <int G, class T>
 __device__ __forceinline__ uint64_t shared_from(const KParams& p, uint64_t r, uint64_t a0, int gib, uint64_t ngroups) {
-    constexpr bool SHARE = IMPLICIT && LINE && MODE == MODE_EMIT && !NOSHARE;
+    constexpr bool SHARE = T::IMPLICIT && T::LINE && T::MODE == MODE_EMIT && !T::NOSHARE;
     constexpr int GPW = 64 / G;  // groups per wavefront
     if (!SHARE || p.stride < 384 || (gib % GPW) == GPW - 1 || r + 1 >= p.n || r + 1 >= ngroups ||
         r + 1 + ngroups < p.n)
@@ -703,21 +695,14 @@ __device__ __forceinline__ uint64_t shared_from(const KParams& p, uint64_t r, ui
 
 // One step of the walk: prefetch the following step into `nx`, then sum `cv` (the current step)
 // and finish the record on its last step.  Returns false when the group has no more work.
-template <int G, int U, int MODE, bool IMPLICIT, bool NT, bool PF, bool SKIPD, bool LINE, bool NHC, int CU = 0,
-          bool SHUF = false, bool WHOLE = false, bool SHUF2 = false, bool SEGW = false, bool SEGG = false,
-          bool SEGB = false, bool SEG6 = false, int SEGOPT = 0, int VAR = 0, bool FLD = false>
-__device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MODE == MODE_COPY>& cv,
-                                          Regs<U, MODE == MODE_COPY>& nx, int lane, uint64_t ngroups, u32x4* win,
-                                          int gib, SegInfo* si = nullptr, SegInfoG* sg = nullptr,
-                                          bool blockwide = false) {
-    constexpr bool COPY = MODE == MODE_COPY;
-    // where the record geometry lives (Walk::g / Walk::gr): registers for emit with the register
-    // prefetch, LDS otherwise
-    constexpr bool GREG = MODE == MODE_EMIT && PF && !VarT<VAR>::GLDS;
-    constexpr bool NOSHARE = VarT<VAR>::NOSHARE;
-    constexpr bool NOSTORE = VarT<VAR>::NOSTORE;
-    constexpr bool BSEG = VarT<VAR>::BSEG && MODE == MODE_EMIT && IMPLICIT && LINE && !NHC;
-    constexpr bool SEGF = SEGW || BSEG;  // the finish writes the decided segments whole
+template <int G, int U, class T>
+__device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, T::COPY>& cv, Regs<U, T::COPY>& nx, int lane,
+                                          uint64_t ngroups, u32x4* win, int gib, SegInfo* si, SegInfoG* sg,
+                                          bool blockwide) {
+    constexpr int MODE = T::MODE, SEGOPT = T::SEGOPT;
+    constexpr bool IMPLICIT = T::IMPLICIT, NHC = T::NHC, COPY = T::COPY, PF = T::PF, LINE = T::LINE, SHUF = T::SHUF,
+                   SHUF2 = T::SHUF2, WHOLE = T::WHOLE, GREG = T::GREG, NOSTORE = T::NOSTORE, SEGW = T::SEGW,
+                   SEGG = T::SEGG, SEGB = T::SEGB, SEG6 = T::SEG6, BSEG = T::BSEG, SEGF = T::SEGF;
     constexpr int WIN = Grid<LINE>::WIN;
     constexpr int WIN_CH = Grid<LINE>::WIN_CH;
     static_assert(G * U >= WIN_CH, "step 0 must cover the LDS window");
@@ -731,9 +716,9 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
     const uint32_t step2 = last ? 0u : w.step + 1;
     // SKIPD: no prefetch when the group has nothing left (one record per group in a natural grid:
     // every record's last step would otherwise issue U loads of the dummy line)
-    if (PF && (!SKIPD || have2))
-        load_step<G, U, NT, COPY, LINE, CU, SHUF, SHUF2>(nx, rec2, nch2, step2, lane, have2, (uint64_t)p.dummy,
-                                            shared_from<G, MODE, IMPLICIT, LINE, NOSHARE>(p, r2, rec2.a0, gib, ngroups));
+    if (PF && (!T::SKIPD || have2))
+        load_step<G, U, T, T::CACHED_U>(nx, rec2, nch2, step2, lane, have2, (uint64_t)p.dummy,
+                                        shared_from<G, T>(p, r2, rec2.a0, gib, ngroups));
     // descriptor of the record after next (clamped index: an unconditional load)
     RecRef nxt2 = w.nxt;
     {
@@ -865,7 +850,7 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
             if constexpr (SEGF) w.segA = w.segB = SEG_NONE;
             // SEGOPT / BSEG_NO4: whether the wavefront holds an IPv4 record (one ballot)
             const bool any4 = (SEGW && (SEGOPT & 1)) ? __any(g.fam == 4) : true;
-            if (BSEG && (!VarT<VAR>::BSEG_NO4 || !any4)) {
+            if (BSEG && (!T::BSEG_NO4 || !any4)) {
                 // Whole field segments, decided by one ballot.  A segment that starts before the
                 // record also holds record r-1's last bytes; it goes out whole only when r-1 has no
                 // field in its last 64 bytes (then no store of r-1's group can fall into it).  Each
@@ -874,18 +859,13 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
                 // A record whose fields end 64 bytes or more before its end never reaches into r+1
                 // with its own segments.  The first group of a wavefront, a gapped stride and r = 0
                 // keep the 2-B store for a segment that starts before the record.
-                uint32_t f[3], lo = NO_FIELD, hi = 0;
-                emit_fields(g, f);
-                for (int j = 0; j < 3; ++j)
-                    if (f[j] != NO_FIELD) {
-                        lo = f[j] < lo ? f[j] : lo;
-                        hi = f[j] + 2 > hi ? f[j] + 2 : hi;
-                    }
+                uint32_t lo, hi;
+                field_range(g, lo, hi);
                 const bool ok_tail = hi == 0 || hi + 64 <= w.cur.len;
                 const uint64_t okm = __ballot(lane == 0 && ok_tail);
                 constexpr int GPW = 64 / G;
                 const bool natural = ngroups >= p.n;
-                const bool fam_ok = g.fam == 4 || (VarT<VAR>::BSEG6 && g.fam == 6);
+                const bool fam_ok = g.fam == 4 || (T::BSEG6 && g.fam == 6);
                 if (natural && fam_ok && hi != 0 && ok_tail && w.cur.len < (1u << 29)) {
                     const uint32_t wl = (uint32_t)(threadIdx.x & 63u);
                     const bool prev_ok = (gib % GPW) != 0 && w.r > 0 && p.len == p.stride &&
@@ -901,13 +881,8 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
             if (SEGW && any4) {
                 // publish every field finish_gates may write (a superset is safe), then decide which
                 // of this record's field segments go out whole (see the finish below)
-                uint32_t f[3], lo = NO_FIELD, hi = 0;
-                emit_fields(g, f);
-                for (int j = 0; j < 3; ++j)
-                    if (f[j] != NO_FIELD) {
-                        lo = f[j] < lo ? f[j] : lo;
-                        hi = f[j] + 2 > hi ? f[j] + 2 : hi;
-                    }
+                uint32_t lo, hi;
+                field_range(g, lo, hi);
                 if (lane == 0) {
                     SegInfo e;
                     e.tag = e.tag2 = (uint32_t)w.r;
@@ -992,13 +967,7 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
                         keep &= ~byte_mask(f0, f0 + 2, i);
                         keep &= ~byte_mask(f1, f1 + 2, i);
                         keep &= ~byte_mask(f2, f2 + 2, i);
-                        if (keep == 0xffffffffu) {
-                            *(GMEM uint32_t*)(dst + 4 * i) = cw[i];
-                        } else if (keep) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j)
-                                if (keep & (0xffu << (8 * j))) dst[4 * i + j] = (uint8_t)(cw[i] >> (8 * j));
-                        }
+                        store_dword_masked(dst + 4 * i, cw[i], keep);
                     }
                 }
             }
@@ -1007,7 +976,7 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
 
     // ---- sum this step's chunks over [0, s1) (data: [0, len)) ----
     const int s1 = w.s1;
-    const uint64_t lim = shared_from<G, MODE, IMPLICIT, LINE, NOSHARE>(p, w.r, w.cur.a0, gib, ngroups);
+    const uint64_t lim = shared_from<G, T>(p, w.r, w.cur.a0, gib, ngroups);
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const uint32_t k = w.step * (G * U) + u * G + lane;
@@ -1044,16 +1013,8 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
             const Geom& g = GREG ? w.gr : *w.g;
             const uint64_t a0 = w.cur.a0;
             const int32_t len = (int32_t)w.cur.len;
-            uint32_t lo = NO_FIELD, hi = 0;
-            {
-                uint32_t f[3];
-                emit_fields(g, f);
-                for (int j = 0; j < 3; ++j)
-                    if (f[j] != NO_FIELD) {
-                        lo = f[j] < lo ? f[j] : lo;
-                        hi = f[j] + 2 > hi ? f[j] + 2 : hi;
-                    }
-            }
+            uint32_t lo, hi;
+            field_range(g, lo, hi);
             if (lane == 0) {
                 SegInfoG& e = sg[gib];
                 e.tag = (uint32_t)w.r;
@@ -1145,7 +1106,7 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
                 if (sb != SEG_NONE) wsB = w.cur.a0 + (int64_t)sb;
             }
             finish_gates<G, MODE, NHC, decltype(rd), ((COPY && WHOLE) || SEGF || SEGG) ? WIN : 0, SEGF || SEGG, NOSTORE,
-                         false, false, FLD>(
+                         false, false, T::FIELDS>(
                 p, GREG ? w.gr : *w.g, w.acc, rd, winb, head, w.cur.a0, r, lane, reinterpret_cast<uint8_t*>(win),
                 wsA, wsB);
             if constexpr (SEGF || SEGG) {
@@ -1155,7 +1116,7 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
                     auto seg_store = [&](uint64_t d) {
                         const u32x2 x = *reinterpret_cast<const u32x2*>(winb + (d - base));
                         if constexpr (NOSTORE) asm volatile("" ::"v"(x), "v"(d));
-                        else if constexpr (VarT<VAR>::NTSEG)  // write-through non-temporal vector store
+                        else if constexpr (T::NTSEG)  // write-through non-temporal vector store
                             asm volatile("global_store_dwordx2 %0, %1, off sc1 nt" ::"v"(d), "v"(x) : "memory");
                         else *(GMEM u32x2*)d = x;
                     };
@@ -1176,16 +1137,7 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
                     } else {
                         const uint32_t cw[4] = {c.x, c.y, c.z, c.w};
 #pragma unroll
-                        for (int i = 0; i < 4; ++i) {
-                            const uint32_t keep = byte_mask(lo, hi, i);
-                            if (keep == 0xffffffffu) {
-                                *(GMEM uint32_t*)(dst + 4 * i) = cw[i];
-                            } else if (keep) {
-#pragma unroll
-                                for (int j = 0; j < 4; ++j)
-                                    if (keep & (0xffu << (8 * j))) dst[4 * i + j] = (uint8_t)(cw[i] >> (8 * j));
-                            }
-                        }
+                        for (int i = 0; i < 4; ++i) store_dword_masked(dst + 4 * i, cw[i], byte_mask(lo, hi, i));
                     }
                 }
             }
@@ -1203,59 +1155,37 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, MOD
 }
 
 // MODE_DATA: checksum::data over [0, len).  MODE_EMIT / MODE_VERIFY: the protocol gates.
-// MODE_COPY: payload copy + emit in one pass.  VAR: see VarT.
-// Occupancy floor (waves per SIMD): variant 28 is 27 held to 7 waves, the occupancy of variant 13 at
-// 16 x 4 (descriptor batches); the segment decision's registers otherwise cost it two waves.
-template <int VAR, int MODE>
-struct MinWaves {
-    static constexpr int value = (MODE == MODE_EMIT && VAR == 28) ? 7 : 1;
-};
-
-template <int G, int U, int MODE, bool IMPLICIT, int VAR, bool NHC = false>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MinWaves<VAR, MODE>::value))) void csum_kernel(KParams p) {
-    constexpr bool NT = VarT<VAR>::NT;
-    constexpr bool PF = VarT<VAR>::PF;
-    constexpr bool LINE = VarT<VAR>::LINE;
-    constexpr int CU = VarT<VAR>::CACHED_U;
-    constexpr bool SHUF = VarT<VAR>::SHUF;
-    constexpr bool WHOLE = VarT<VAR>::WHOLE;
-    constexpr bool SHUF2 = VarT<VAR>::SHUF2;
-    // Fixed-stride batches: no prefetch once the group has nothing left (one record per group in
-    // a natural grid), measured 1-1.5 % faster (C2 verify 0.2444 -> 0.2422 ms, C4 0.2219 -> 0.2189
-    // ms).  Descriptor batches keep the unconditional prefetch: there the conditional load made
-    // C3 verify 25 % slower (0.810 -> 0.989 ms).
-    constexpr bool SKIPD = IMPLICIT;
-    constexpr bool COPY = MODE == MODE_COPY;
+// MODE_COPY: payload copy + emit in one pass.  Form: csum_variants.h (read through WalkTraits).
+template <int G, int U, int MODE, bool IMPLICIT, class Form, bool NHC>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(Form::MIN_WAVES))) void csum_kernel(KParams p) {
+    typedef WalkTraits<Form, MODE, IMPLICIT, NHC> T;
+    constexpr bool COPY = T::COPY;
     constexpr int GPB = 256 / G;
     static_assert(G >= 8 && G <= 64 && (G & (G - 1)) == 0, "group size");
-    __shared__ u32x4 win[GPB][Grid<LINE>::WIN_CH];
+    __shared__ u32x4 win[GPB][Grid<T::LINE>::WIN_CH];
     __shared__ Geom geo[GPB];
-    constexpr bool SEGW = VarT<VAR>::SEGW && MODE == MODE_EMIT && IMPLICIT && LINE && !NHC;
-    constexpr bool SEGG = VarT<VAR>::SEGG && MODE == MODE_EMIT && LINE && !NHC;
-    constexpr bool SEGB = SEGG && VarT<VAR>::SEGB;
-    constexpr bool SEG6 = SEGG && VarT<VAR>::SEG6;
-    __shared__ SegInfo segi[SEGW ? GPB : 1];
-    __shared__ SegInfoG segg[SEGG ? GPB : 1];
+    __shared__ SegInfo segi[T::SEGW ? GPB : 1];
+    __shared__ SegInfoG segg[T::SEGG ? GPB : 1];
 
     const int lane = (int)(threadIdx.x % G);
     const int gib = (int)(threadIdx.x / G);
     const uint64_t ngroups = (uint64_t)gridDim.x * GPB;
-    if constexpr (SEGW) {
+    if constexpr (T::SEGW) {
         if (lane == 0) segi[gib].tag = segi[gib].tag2 = ~0u;  // no record yet (read by the neighbours)
     }
-    if constexpr (SEGG) {
+    if constexpr (T::SEGG) {
         if (lane == 0) segg[gib].tag = ~0u;
     }
     // SEGB: a natural grid (one record per group) and a full workgroup, the same for every wave of
     // the workgroup, so that each of them reaches the barrier after the parse exactly once
     const uint64_t bid = logical_block(p.xcd_remap);
-    const bool blockwide = SEGB && ngroups >= p.n && bid * GPB + GPB <= p.n;
+    const bool blockwide = T::SEGB && ngroups >= p.n && bid * GPB + GPB <= p.n;
     Walk w;
     w.r = bid * GPB + gib;
     if (w.r >= p.n) return;
     w.cur = rec_at<IMPLICIT, COPY, NHC>(p, w.r);
     w.nxt = rec_at<IMPLICIT, COPY, NHC>(p, w.r + ngroups < p.n ? w.r + ngroups : p.n - 1);
-    w.nch = n_chunks<LINE>(w.cur);
+    w.nch = n_chunks<T::LINE>(w.cur);
     w.step = 0;
     // The record geometry: in LDS, except for emit.  Measured (tools/gpu_ab.sh, MI355X): in LDS,
     // C4 verify 0.2167 -> 0.2044 ms (8 x 6: 113 -> 95 VGPRs, 4 -> 5 waves/SIMD) but C4 emit
@@ -1269,295 +1199,68 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(MinWaves<VA
     w.segA = w.segB = SEG_NONE;
 
     Regs<U, COPY> va;
-    if (PF) {
+    if (T::PF) {
         Regs<U, COPY> vb;
-        load_step<G, U, NT, COPY, LINE, (VarT<VAR>::CU0 ? VarT<VAR>::CU0 : CU), SHUF>(va, w.cur, w.nch, 0, lane, true, (uint64_t)p.dummy,
-                                                  shared_from<G, MODE, IMPLICIT, LINE, VarT<VAR>::NOSHARE>(p, w.r, w.cur.a0, gib, ngroups));
+        load_step<G, U, T, (T::CU0 ? T::CU0 : T::CACHED_U)>(va, w.cur, w.nch, 0, lane, true, (uint64_t)p.dummy,
+                                                           shared_from<G, T>(p, w.r, w.cur.a0, gib, ngroups));
         // the body is instantiated twice with the register sets' roles swapped
         while (true) {
-            if (!walk_step<G, U, MODE, IMPLICIT, NT, PF, SKIPD, LINE, NHC, CU, SHUF, false, false, SEGW, SEGG, SEGB, SEG6,
-                           VarT<VAR>::SEGOPT, VAR>(p, w, va, vb, lane, ngroups, &win[gib][0], gib, segi, segg, blockwide)) break;
-            if (!walk_step<G, U, MODE, IMPLICIT, NT, PF, SKIPD, LINE, NHC, CU, SHUF, false, false, SEGW, SEGG, SEGB, SEG6,
-                           VarT<VAR>::SEGOPT, VAR>(p, w, vb, va, lane, ngroups, &win[gib][0], gib, segi, segg, blockwide)) break;
+            if (!walk_step<G, U, T>(p, w, va, vb, lane, ngroups, &win[gib][0], gib, segi, segg, blockwide)) break;
+            if (!walk_step<G, U, T>(p, w, vb, va, lane, ngroups, &win[gib][0], gib, segi, segg, blockwide)) break;
         }
     } else {
         while (true) {
-            load_step<G, U, NT, COPY, LINE, 0, SHUF, SHUF2>(va, w.cur, w.nch, w.step, lane, true, (uint64_t)p.dummy,
-                                                            shared_from<G, MODE, IMPLICIT, LINE, VarT<VAR>::NOSHARE>(p, w.r, w.cur.a0, gib, ngroups));
-            if (!walk_step<G, U, MODE, IMPLICIT, NT, PF, SKIPD, LINE, NHC, 0, SHUF, WHOLE, SHUF2, false, SEGG, SEGB, SEG6, 0, VAR>(
-                    p, w, va, va, lane, ngroups, &win[gib][0], gib, nullptr, segg, blockwide)) break;
-        }
-    }
-}
-
-// emit_fields' walk form (smol_csum_batch_emit_fields, any batch): csum_kernel's variant-5 emit walk —
-// the line grid, non-temporal loads, the register prefetch and, over fixed strides, the shared
-// boundary lines (shared_from) — finishing through the fields sink (finish_gates FLD).  None of the
-// whole-segment machinery: it only shapes writes into the records, and this kernel writes none.
-template <int G, int U, bool IMPLICIT>
-__global__ __launch_bounds__(256) void csum_fields_kernel(KParams p) {
-    constexpr int VAR = 5;
-    static_assert(VarT<VAR>::NT && VarT<VAR>::PF && VarT<VAR>::LINE && !VarT<VAR>::SEGW && !VarT<VAR>::SEGG &&
-                      !VarT<VAR>::BSEG, "the walk's plain line-grid form");
-    constexpr int GPB = 256 / G;
-    __shared__ u32x4 win[GPB][Grid<true>::WIN_CH];
-    __shared__ Geom geo[GPB];
-    const int lane = (int)(threadIdx.x % G);
-    const int gib = (int)(threadIdx.x / G);
-    const uint64_t ngroups = (uint64_t)gridDim.x * GPB;
-    Walk w;
-    w.r = logical_block(p.xcd_remap) * GPB + gib;
-    if (w.r >= p.n) return;
-    w.cur = rec_at<IMPLICIT, false>(p, w.r);
-    w.nxt = rec_at<IMPLICIT, false>(p, w.r + ngroups < p.n ? w.r + ngroups : p.n - 1);
-    w.nch = n_chunks<true>(w.cur);
-    w.step = 0;
-    w.g = &geo[gib];
-    w.gr = Geom{};
-    w.s1 = 0;
-    w.acc = w.acc2 = 0;
-    w.fip = w.fl4 = w.fin = NO_FIELD;
-    w.far = false;
-    w.segA = w.segB = SEG_NONE;
-    Regs<U, false> va, vb;
-    load_step<G, U, true, false, true>(va, w.cur, w.nch, 0, lane, true, (uint64_t)p.dummy,
-                                       shared_from<G, MODE_EMIT, IMPLICIT, true>(p, w.r, w.cur.a0, gib, ngroups));
-    // the body is instantiated twice with the register sets' roles swapped (csum_kernel)
-    while (true) {
-        if (!walk_step<G, U, MODE_EMIT, IMPLICIT, true, true, IMPLICIT, true, false, 0, false, false, false, false, false,
-                       false, false, 0, VAR, true>(p, w, va, vb, lane, ngroups, &win[gib][0], gib)) break;
-        if (!walk_step<G, U, MODE_EMIT, IMPLICIT, true, true, IMPLICIT, true, false, 0, false, false, false, false, false,
-                       false, false, 0, VAR, true>(p, w, vb, va, lane, ngroups, &win[gib][0], gib)) break;
-    }
-}
-
-// The shapes auto_shape gives variant 5: fixed strides by record length, descriptors 16 x 3.
-template <int G, int U, bool IMPLICIT>
-hipError_t launch_fields_one(const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    constexpr uint32_t GPB = 256 / G;
-    const uint32_t blocks = grid_blocks((p.n + GPB - 1) / GPB, max_blocks);
-    note_launch(KERN_WALK_FIELDS, 0, G, U);
-    hipLaunchKernelGGL((csum_fields_kernel<G, U, IMPLICIT>), dim3(blocks), dim3(256), 0, s, p);
-    return hipGetLastError();
-}
-
-template <bool IMPLICIT>
-hipError_t launch_walk_fields(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    if constexpr (!IMPLICIT) {
-        return launch_fields_one<16, 3, false>(p, max_blocks, s);
-    } else {
-        switch (shape) {
-            case CFG_G8U6: return launch_fields_one<8, 6, true>(p, max_blocks, s);
-            case CFG_G8U7: return launch_fields_one<8, 7, true>(p, max_blocks, s);
-            case CFG_G16U6: return launch_fields_one<16, 6, true>(p, max_blocks, s);
-            case CFG_G32U4: return launch_fields_one<32, 4, true>(p, max_blocks, s);
-            default: return launch_fields_one<64, 4, true>(p, max_blocks, s);
+            load_step<G, U, T, 0>(va, w.cur, w.nch, w.step, lane, true, (uint64_t)p.dummy,
+                                  shared_from<G, T>(p, w.r, w.cur.a0, gib, ngroups));
+            if (!walk_step<G, U, T>(p, w, va, va, lane, ngroups, &win[gib][0], gib, nullptr, segg, blockwide)) break;
         }
     }
 }
 
 // ---------------------------------------------------------------------------------------------
-// Launch table
+// Launch
 // ---------------------------------------------------------------------------------------------
 
-template <int G, int U, int MODE, bool IMPLICIT, int VAR, bool NHC = false>
-hipError_t launch_one(const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    constexpr uint32_t GPB = 256 / G;
-    const uint64_t want = (p.n + GPB - 1) / GPB;
-    const uint32_t blocks = grid_blocks(want, max_blocks);
-    note_launch(NHC ? KERN_WALK_NHC : KERN_WALK, VAR, G, U);
-    hipLaunchKernelGGL((csum_kernel<G, U, MODE, IMPLICIT, VAR, NHC>), dim3(blocks), dim3(256), 0, s, p);
-    return hipGetLastError();
+// The launch of (variant, shape) for this (mode, batch form): the kernel, the number reported and the
+// shape all come from csum_launch.h's with_walk_kernel (the registry's rows and the shape mappers).
+template <int MODE, bool IMPLICIT, bool NHC>
+hipError_t launch_walk_kernel(int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;
+    with_walk_kernel<MODE, IMPLICIT, NHC>(var, shape, [&](auto form, auto num, auto g, auto u) {
+        constexpr int G = decltype(g)::value, U = decltype(u)::value;
+        const uint32_t blocks = grid_blocks((p.n + 256 / G - 1) / (256 / G), max_blocks);
+        note_launch(NHC ? KERN_WALK_NHC : KERN_WALK, decltype(num)::value, G, U);
+        hipLaunchKernelGGL((csum_kernel<G, U, MODE, IMPLICIT, decltype(form), NHC>), dim3(blocks), dim3(256), 0, s, p);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
-template <int MODE, bool IMPLICIT, int VAR>
-hipError_t launch_shape(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    switch (shape) {
-        case CFG_G8U6: return launch_one<8, 6, MODE, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G8U7: return launch_one<8, 7, MODE, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G16U3: return launch_one<16, 3, MODE, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G16U4: return launch_one<16, 4, MODE, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G16U6: return launch_one<16, 6, MODE, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G32U3: return launch_one<32, 3, MODE, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G32U4: return launch_one<32, 4, MODE, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G64U2: return launch_one<64, 2, MODE, IMPLICIT, VAR>(p, max_blocks, s);
-        default: return launch_one<64, 4, MODE, IMPLICIT, VAR>(p, max_blocks, s);
-    }
-}
-
-// The whole-segment emit variants (23-27) are built for the shapes emit picks (8 x 6 / 8 x 7 at a
-// fixed stride, 16 x 3 / 16 x 4 over descriptors) and 32 x 4 / 64 x 4 for long records; the other
-// shapes map to the one with the same group size.
-template <bool IMPLICIT, int VAR>
-hipError_t launch_seg_shape(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    switch (shape) {
-        case CFG_G8U6: return launch_one<8, 6, MODE_EMIT, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G8U7: return launch_one<8, 7, MODE_EMIT, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G16U3: return launch_one<16, 3, MODE_EMIT, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G16U4:
-        case CFG_G16U6: return launch_one<16, 4, MODE_EMIT, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G32U3:
-        case CFG_G32U4: return launch_one<32, 4, MODE_EMIT, IMPLICIT, VAR>(p, max_blocks, s);
-        default: return launch_one<64, 4, MODE_EMIT, IMPLICIT, VAR>(p, max_blocks, s);
-    }
-}
-
-#ifdef SMOL_EXP
-// Experiment variants of fixed-stride emit (31-38, and 64 + 5 without stores): the two fixed-stride
-// shapes only (other shapes map to the one with the same group size).
-template <int VAR>
-hipError_t launch_emit_exp(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    if (shape == CFG_G8U6) return launch_one<8, 6, MODE_EMIT, true, VAR>(p, max_blocks, s);
-    return launch_one<8, 7, MODE_EMIT, true, VAR>(p, max_blocks, s);
-}
-
-// The experiments build (SMOL_EXP): every walk variant that was measured and is not a default.
-template <int MODE, bool IMPLICIT>
-hipError_t launch_walk_exp(int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    if constexpr (MODE == MODE_EMIT && IMPLICIT) {
-        switch (var) {
-            case 31: return launch_emit_exp<31>(shape, p, max_blocks, s);
-            case 32: return launch_emit_exp<32>(shape, p, max_blocks, s);
-            case 33: return launch_emit_exp<33>(shape, p, max_blocks, s);
-            case 34: return launch_emit_exp<34>(shape, p, max_blocks, s);
-            case 35: return launch_emit_exp<35>(shape, p, max_blocks, s);
-            case 36: return launch_emit_exp<36>(shape, p, max_blocks, s);
-            case 37: return launch_emit_exp<37>(shape, p, max_blocks, s);
-            case 38: return launch_emit_exp<38>(shape, p, max_blocks, s);
-            case 40: return launch_emit_exp<40>(shape, p, max_blocks, s);
-            case 12: return launch_emit_exp<12>(shape, p, max_blocks, s);
-            case 14: return launch_emit_exp<14>(shape, p, max_blocks, s);
-            case 64 + 5: return launch_emit_exp<64 + 5>(shape, p, max_blocks, s);  // (the one | 64 number the walk kernel still owns)
-            default: break;
-        }
-    }
-    switch (var) {
-        case 1: return launch_shape<MODE, IMPLICIT, 1>(shape, p, max_blocks, s);
-        case 2: return launch_shape<MODE, IMPLICIT, 2>(shape, p, max_blocks, s);
-        case 6: return launch_shape<MODE, IMPLICIT, 6>(shape, p, max_blocks, s);
-        case 19: return launch_shape<MODE, IMPLICIT, 19>(shape, p, max_blocks, s);
-        case 29:  // round 4's fixed-stride emit default
-            if constexpr (MODE == MODE_EMIT && IMPLICIT) return launch_seg_shape<IMPLICIT, 29>(shape, p, max_blocks, s);
-            return launch_shape<MODE, IMPLICIT, 5>(shape, p, max_blocks, s);
-        case 23:
-        case 24:
-        case 25:
-        case 26:
-        case 27:
-        case 28:
-            if constexpr (MODE == MODE_EMIT) {
-                switch (var) {
-                    case 23: return launch_seg_shape<IMPLICIT, 23>(shape, p, max_blocks, s);
-                    case 24: return launch_seg_shape<IMPLICIT, 24>(shape, p, max_blocks, s);
-                    case 25: return launch_seg_shape<IMPLICIT, 25>(shape, p, max_blocks, s);
-                    case 26: return launch_seg_shape<IMPLICIT, 26>(shape, p, max_blocks, s);
-                    case 27: return launch_seg_shape<IMPLICIT, 27>(shape, p, max_blocks, s);
-                    default: return launch_seg_shape<IMPLICIT, 28>(shape, p, max_blocks, s);
-                }
-            }
-            return var >= 26 ? launch_shape<MODE, IMPLICIT, 13>(shape, p, max_blocks, s)
-                             : launch_shape<MODE, IMPLICIT, 5>(shape, p, max_blocks, s);
-        case 9:
-        case 10:
-            if constexpr (MODE == MODE_EMIT && IMPLICIT) {
-                return var == 9 ? launch_shape<MODE, IMPLICIT, 9>(shape, p, max_blocks, s)
-                                : launch_shape<MODE, IMPLICIT, 10>(shape, p, max_blocks, s);
-            }
-            return launch_shape<MODE, IMPLICIT, 5>(shape, p, max_blocks, s);
-        case 0: return launch_shape<MODE, IMPLICIT, 0>(shape, p, max_blocks, s);
-        case 31: case 32: case 33: case 34: case 35: case 36: case 37: case 38: case 40: case 12: case 14:
-            return launch_shape<MODE, IMPLICIT, 5>(shape, p, max_blocks, s);  // emit variants: 5 elsewhere
-        default: return hipErrorInvalidValue;
-    }
-}
-#endif
-
-// The product variants (variants.def, build P): 5 (line grid, nt loads, register prefetch),
-// 13 (5 without the prefetch) and, for fixed-stride emit, 39 (5 with whole field segments: 29's
-// LDS-published decision on wavefronts with an IPv4 record, one ballot on the others).  Other
-// variants: the experiments build.
 template <int MODE, bool IMPLICIT>
 hipError_t launch_walk(int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    switch (var) {
-        case 5: return launch_shape<MODE, IMPLICIT, 5>(shape, p, max_blocks, s);
-        case 13: return launch_shape<MODE, IMPLICIT, 13>(shape, p, max_blocks, s);
-        case 39:
-            if constexpr (MODE == MODE_EMIT && IMPLICIT) return launch_seg_shape<IMPLICIT, 39>(shape, p, max_blocks, s);
-            return launch_shape<MODE, IMPLICIT, 5>(shape, p, max_blocks, s);
-        default:
-#ifdef SMOL_EXP
-            return launch_walk_exp<MODE, IMPLICIT>(shape, var, p, max_blocks, s);
-#else
-            return hipErrorInvalidValue;
-#endif
-    }
+    return launch_walk_kernel<MODE, IMPLICIT, false>(shape, var, p, max_blocks, s);
 }
 
-// 6LoWPAN NHC UDP batches: the walk kernel instantiated with the NHC gates, on the two default
-// variants (1: 16-B grid, cached loads; 5: line grid, nt loads) and three shapes (other shapes map
-// to the one with the same group size or the nearest).
+// 6LoWPAN NHC UDP batches: the walk kernel with the NHC gates.
 template <int MODE, bool IMPLICIT>
 hipError_t launch_walk_nhc(int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    const int g = (shape == CFG_G8U6 || shape == CFG_G8U7) ? shape : CFG_G16U3;
-    // the registry's V_NHC_LINE variants (the descriptor-verify default 13 included) run variant 5 here
-    if (variant_is(var, V_NHC_LINE)) {
-        if (g == CFG_G8U6) return launch_one<8, 6, MODE, IMPLICIT, 5, true>(p, max_blocks, s);
-        if (g == CFG_G8U7) return launch_one<8, 7, MODE, IMPLICIT, 5, true>(p, max_blocks, s);
-        return launch_one<16, 3, MODE, IMPLICIT, 5, true>(p, max_blocks, s);
-    }
-    if (g == CFG_G8U6) return launch_one<8, 6, MODE, IMPLICIT, 1, true>(p, max_blocks, s);
-    if (g == CFG_G8U7) return launch_one<8, 7, MODE, IMPLICIT, 1, true>(p, max_blocks, s);
-    return launch_one<16, 3, MODE, IMPLICIT, 1, true>(p, max_blocks, s);
+    return launch_walk_kernel<MODE, IMPLICIT, true>(shape, var, p, max_blocks, s);
 }
 
-// MODE_COPY keeps three chunks per lane and step (record + two source chunks), so it is built for
-// the U <= 3 shapes only (wider shapes map to the same group size with fewer chunks) and for the
-// plain-load variants on the 16-byte grid.  (Copy-emit's default is now variant 17, copy_kernel in
-// csum_copy.hip.)  Without the register prefetch (variant 8, round 1's default)
-// the kernel needs fewer VGPRs and runs more waves per SIMD: C2 copy-emit 0.95 -> 0.85 ms on
-// MI355X (tools/gpu_exp.sh sweep, profiles/r01_kernel_stats_c2copy.csv); variant 1 keeps the
-// prefetch for comparison.
-template <bool IMPLICIT, int VAR>
-hipError_t launch_copy_var(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    switch (shape) {
-        case CFG_G8U6:
-        case CFG_G8U7: return launch_one<8, 3, MODE_COPY, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G32U3:
-        case CFG_G32U4: return launch_one<32, 3, MODE_COPY, IMPLICIT, VAR>(p, max_blocks, s);
-        case CFG_G64U2:
-        case CFG_G64U4: return launch_one<64, 2, MODE_COPY, IMPLICIT, VAR>(p, max_blocks, s);
-        default: return launch_one<16, 3, MODE_COPY, IMPLICIT, VAR>(p, max_blocks, s);
-    }
-}
-
-// variant 17: the class-split copy-emit kernel (csum_copy.hip)
-hipError_t launch_copy_v17(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s);
-// variant 21: variant 17 with the first body round's loads ahead of round 1's stores (csum_copy.hip)
-hipError_t launch_copy_v21(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s);
-#ifdef SMOL_EXP
-// variants 30 / 22: 21 with non-temporal body stores / and source loads (csum_copy.hip)
-hipError_t launch_copy_nt(int var, const KParams& p, uint32_t max_blocks, hipStream_t s);
-#endif
-
-// 17 / 21 (copy_kernel) are the product's; the walk kernel's MODE_COPY variants (1, 8, 11, 16: the
-// round-1 / 2 designs) are in the experiments build only.
+// emit_fields' walk form (smol_csum_batch_emit_fields, any batch): variant 5's emit walk finishing through
+// the fields sink (WFields; finish_gates FLD), on the shapes auto_shape gives variant 5.  Outside the
+// registry: csum_dispatch.h pick_fields chooses it, and it is reported as KERN_WALK_FIELDS, variant 0.
 template <bool IMPLICIT>
-hipError_t launch_copy(int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    switch (var) {
-        case 17: return launch_copy_v17(shape, p, max_blocks, s);
-        case 21: return launch_copy_v21(shape, p, max_blocks, s);
-#ifdef SMOL_EXP
-        case 30:
-        case 98:
-        case 102:
-        case 22: return launch_copy_nt(var, p, max_blocks, s);
-        case 1: return launch_copy_var<IMPLICIT, 1>(shape, p, max_blocks, s);
-        case 11: return launch_copy_var<IMPLICIT, 11>(shape, p, max_blocks, s);
-        case 8: return launch_copy_var<IMPLICIT, 8>(shape, p, max_blocks, s);
-        case 16: return launch_copy_var<IMPLICIT, 16>(shape, p, max_blocks, s);
-#endif
-        default: return hipErrorInvalidValue;
-    }
+hipError_t launch_walk_fields(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;
+    with_walk_shape<IMPLICIT ? S_FIXED5 : S_G16U3>(shape, [&](auto g, auto u) {
+        constexpr int G = decltype(g)::value, U = decltype(u)::value;
+        const uint32_t blocks = grid_blocks((p.n + 256 / G - 1) / (256 / G), max_blocks);
+        note_launch(KERN_WALK_FIELDS, 0, G, U);
+        hipLaunchKernelGGL((csum_kernel<G, U, MODE_EMIT, IMPLICIT, WFields, false>), dim3(blocks), dim3(256), 0, s, p);
+        e = hipGetLastError();
+    });
+    return e;
 }
 
 }  // namespace smolcsum

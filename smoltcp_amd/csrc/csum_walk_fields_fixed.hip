@@ -1,4 +1,4 @@
-// Instantiates emit_fields' walk form (csum_walk.h csum_fields_kernel) for fixed-stride batches.
+// Instantiates emit_fields' walk form (csum_walk.h: csum_kernel with the form WFields) for fixed-stride batches.
 #include "csum_walk.h"
 
 namespace smolcsum {

@@ -244,3 +244,48 @@ def test_kernel_forms_match_recorded_table():
     P = _lib.lib()
     for v in (94, 95, 96):
         assert P.smol_csum_tool_form(v, 1, out) == _lib.SMOL_EINVAL
+
+
+def test_walk_launches_match_recorded_table():
+    """The walk kernel's launcher (smol_csum_tool_walk_launch: the registry switch and the shape mapper
+    that launch_walk / launch_walk_nhc run) launches what the commit before the named walk forms launched.
+    tests/data/walk_launch_parent.jsonl was recorded from that commit, never from the code under test: a
+    program linked against each of its two libraries called smolcsum::launch_csum for every variant
+    0-127, data / emit / verify / copy-emit, fixed-stride and descriptor batches, NHC on and off and all
+    nine launch shapes, ignored the no-device launch error and read smol_csum_tool_last_launch
+    (note_launch runs before the launch), with a sentinel launch of another kernel family between probes
+    to tell the calls that launch nothing apart.  One line per (library, variant, op, batch form, nhc)
+    that launched anything, with the nine packed last_launch values; a missing line is an error for all
+    nine.  Lines whose kernel id is not the walk's (copy_kernel's 17 / 21 / 22 / 30 / 98 / 102) are not
+    the walk launcher's to answer."""
+    import json
+
+    want = {}
+    with open(os.path.join(ROOT, "tests", "data", "walk_launch_parent.jsonl")) as f:
+        for line in f:
+            r = json.loads(line)
+            assert len(r["launch"]) == 9
+            want[(r["lib"], r["variant"], r["op"], r["implicit"], r["nhc"])] = r["launch"]
+    assert len(want) == 1235
+    out = (ctypes.c_int * 4)()
+    served = 0
+    for name, L in _both_libs():
+        assert any(k[0] == name for k in want)
+        for v in range(128):
+            for op in range(4):
+                for implicit in (1, 0):
+                    for nhc in (0, 1):
+                        rec = want.get((name, v, op, implicit, nhc), ["error"] * 9)
+                        for shape in range(9):
+                            rc = L.smol_csum_tool_walk_launch(v, op, implicit, nhc, shape, out)
+                            exp = rec[shape]
+                            where = (name, v, op, implicit, nhc, shape)
+                            if exp != "error" and exp >> 24 in (1, 4):  # KERN_WALK, KERN_WALK_NHC
+                                assert rc == 0, where
+                                assert out[0] << 24 | out[1] << 16 | out[2] << 8 | out[3] == exp, (where, list(out), exp)
+                                served += 1
+                            else:  # and the library serves nothing the recorded commit did not
+                                assert rc == _lib.SMOL_EINVAL, (where, list(out))
+        assert L.smol_csum_tool_walk_launch(5, 4, 1, 0, 0, out) == _lib.SMOL_EINVAL
+        assert L.smol_csum_tool_walk_launch(5, 1, 1, 0, 9, out) == _lib.SMOL_EINVAL
+    assert served > 9 * 1000
