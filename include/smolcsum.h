@@ -25,6 +25,8 @@
  *       - smol_csum_batch_emit_fields == emit's values without the writes: one 16-byte entry per
  *         record (field offsets, values, status) for a caller whose frames stay in host memory and
  *         who patches them there with smol_csum_apply_fields;
+ *       - smol_csum_batch_verify_copy == verify, and in the same pass the UDP / TCP payloads
+ *         delivered to caller-chosen slots of a second device buffer (the socket's rx_buffer copy);
  *       - smol_csum_batch_data   == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
@@ -292,6 +294,67 @@ int smol_csum_batch_emit_fields(smol_csum_ctx_t* ctx, const uint8_t* d_buf, cons
 
 /* host: write the entry's fields into one record; SMOL_ERANGE (nothing written) if a field does not fit in len */
 int smol_csum_apply_fields(uint8_t* rec, uint32_t len, const smol_csum_fields_t* f);
+
+/* ---- verify_copy: verify and deliver the L4 payloads in one pass --------------------------- */
+
+/* Where one record's payload goes (16 bytes, 16-byte-aligned device array, input). */
+typedef struct {
+    uint64_t dst_offset; /* byte offset in d_dst (any alignment)            */
+    uint32_t cap;        /* bytes available there                             */
+    uint32_t reserved;   /* 0; the kernels ignore it                          */
+} smol_csum_slot_t;
+
+/* One record's payload span (8 bytes, 8-byte-aligned device array, output). */
+typedef struct {
+    uint32_t len;     /* payload bytes                                                */
+    uint16_t off;     /* record-relative offset of the payload; 0: the record has none */
+    uint8_t copied;   /* 1: the span is defined and len <= cap (bytes delivered)      */
+    uint8_t reserved; /* 0 */
+} smol_csum_span_t;
+
+/* Verify, and deliver every record's L4 payload to its slot of d_dst, in one pass over the batch.
+ * On receive the reference makes two passes over a payload: UdpRepr::parse / TcpRepr::parse sum the
+ * whole L4 buffer (src/wire/udp.rs:250-257, src/wire/tcp.rs:917-919), then the socket copies the
+ * payload out (UDP: rx_buffer.enqueue + copy_from_slice, src/socket/udp.rs:522-523; TCP:
+ * rx_buffer.write_unallocated, src/socket/tcp.rs:2231).  Here each byte of a record is read once.
+ *
+ * Status.  d_status[i] is exactly the byte smol_csum_batch_verify writes for the same batch and caps.
+ *
+ * Span.  A record has a span when it reaches the UDP or TCP gate and verify's parse marks it neither
+ * SMOL_ST_MALFORMED nor SMOL_ST_UNSUPPORTED (so: no span after a failed check_len, a port-0
+ * rejection, a Hop-by-Hop drop, for a fragment, a SMOL_REC_IPHDR_ONLY record, a non-IP ethertype or
+ * SMOL_KIND_RAW).
+ *   UDP (UdpPacket::payload, udp.rs:153-157): off = L4 offset + 8, len = UDP length field - 8.
+ *   TCP (TcpPacket::payload, tcp.rs:419-423): off = L4 offset + 4 * data offset,
+ *                                             len = L4 buffer length - 4 * data offset.
+ * The L4 buffer is the slice the reference hands the L4 packet: IPv4 total length - IHL * 4 (not the
+ * record length: Ethernet padding is neither summed nor delivered), IPv6 payload length minus a
+ * leading Hop-by-Hop header.  ICMP, IGMP and every rejected record get off = 0, len = 0, copied = 0.
+ *
+ * Copy.  When the span is defined and len <= cap, record bytes [off, off + len) are written to
+ * d_dst[dst_offset .. dst_offset + len) and copied = 1 (len == 0 is trivially copied); otherwise
+ * nothing is stored for the record and copied = 0, the span still reported.
+ * THE COPY DOES NOT WAIT FOR THE CHECKSUM VERDICT: the verdict is known only after the last byte is
+ * summed, and holding a record back would cost the second pass this call exists to remove.  A
+ * record with a bad checksum is delivered as it stands in the buffer.  The caller commits a slot
+ * only when d_status[i] & SMOL_ST_ACCEPT, as with a NIC's receive ring.
+ *
+ * Writes.  No byte of d_dst outside the copied ranges is ever written and no byte of d_dst is ever
+ * read: the first and last piece of a range go out as byte-masked stores, never read-modify-write,
+ * so slots may lie back to back (a neighbouring slot may be written by another wavefront at the
+ * same time).  Slots must not overlap each other or the batch.  d_buf is only read.
+ *
+ * Resources.  No context scratch, no event, no allocation; stream-ordered on `stream`, and calls on
+ * different streams are independent (also on one context).
+ *
+ * SMOL_EINVAL: NULL ctx, bad caps, NULL d_dst / d_slots / d_status / d_spans with n > 0, d_slots
+ * not 16-byte aligned, d_spans not 8-byte aligned.  SMOL_ERANGE: as verify.  n == 0 returns SMOL_OK
+ * and launches nothing.  Not covered: IPv4 fragment groups and the 6LoWPAN NHC entry points.
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive, as emit_fields was). */
+int smol_csum_batch_verify_copy(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
+                                const smol_checksum_caps_t* caps, uint8_t* d_dst, const smol_csum_slot_t* d_slots,
+                                uint8_t* d_status, smol_csum_span_t* d_spans, void* stream);
 
 /* ---- 3. IPv4 fragment groups ------------------------------------------------------------- */
 

@@ -95,6 +95,12 @@ int smol_csum_tool_set_launch_records(smol_csum_ctx_t* ctx, uint64_t records);
  * number. */
 int smol_csum_tool_set_fields_kernel(smol_csum_ctx_t* ctx, int kernel);
 
+/* The body stores of smol_csum_batch_verify_copy: 0 the library's choice (the default cache policy), 1
+ * non-temporal (tools/exp_verify_copy.py measures one against the other).  Its launch shape follows
+ * smol_csum_tool_set_shape, its grid smol_csum_tool_set_max_blocks; smol_csum_tool_set_variant does not
+ * reach it (the kernel has no variant number). */
+int smol_csum_tool_set_vcopy_stores(smol_csum_ctx_t* ctx, int nt);
+
 /* Read-only HBM streaming probe over `bytes` (multiple of 16, 16-byte aligned `d_buf`): the
  * achievable read ceiling that the checksum kernels are compared with.  Each wavefront streams
  * contiguous 8-KiB pieces with eight non-temporal 16-byte loads per lane in flight (the fastest

@@ -31,6 +31,7 @@ ABI_SYMBOLS = [
     "smol_csum_pseudo_header_v6", "smol_csum_pseudo_header", "smol_csum_ctx_create",
     "smol_csum_ctx_destroy", "smol_csum_batch_data", "smol_csum_batch_emit",
     "smol_csum_batch_verify", "smol_csum_batch_copy_emit", "smol_csum_batch_emit_fields",
+    "smol_csum_batch_verify_copy",
     "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
     "smol_csum_batch_verify_frag", "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
@@ -45,13 +46,14 @@ TOOL_SYMBOLS = [
     "smol_csum_tool_variant_built",
     "smol_csum_tool_kernel_name", "smol_csum_tool_kernel_for", "smol_csum_tool_last_launch",
     "smol_csum_tool_pick", "smol_csum_tool_variant_info", "smol_csum_tool_form",
-    "smol_csum_tool_set_fields_kernel", "smol_csum_tool_walk_launch",
+    "smol_csum_tool_set_fields_kernel", "smol_csum_tool_walk_launch", "smol_csum_tool_set_vcopy_stores",
 ]
 # Tool symbols added in later rounds: bound only when the loaded build has them (SMOLCSUM_LIB may name
 # an older build for an A/B run), and a call to a missing one raises AttributeError naming it.
 OPTIONAL_TOOL_SYMBOLS = ("smol_csum_tool_variant_built", "smol_csum_tool_kernel_for", "smol_csum_tool_segment_probe",
                          "smol_csum_tool_pick", "smol_csum_tool_variant_info", "smol_csum_tool_form",
-                         "smol_csum_tool_set_fields_kernel", "smol_csum_tool_walk_launch")
+                         "smol_csum_tool_set_fields_kernel", "smol_csum_tool_walk_launch",
+                         "smol_csum_tool_set_vcopy_stores")
 
 
 class SmolError(RuntimeError):
@@ -100,6 +102,28 @@ class FieldsC(ctypes.Structure):
 
 
 NO_FIELD = 0xFFFF  # SMOL_NO_FIELD
+
+
+class SlotC(ctypes.Structure):
+    """smol_csum_slot_t: where one record's payload goes (smol_csum_batch_verify_copy)."""
+
+    _fields_ = [
+        ("dst_offset", ctypes.c_uint64),
+        ("cap", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
+class SpanC(ctypes.Structure):
+    """smol_csum_span_t: one record's payload span (smol_csum_batch_verify_copy)."""
+
+    _fields_ = [
+        ("len", ctypes.c_uint32),
+        ("off", ctypes.c_uint16),
+        ("copied", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8),
+    ]
+
 
 _LIBS = {}
 
@@ -153,6 +177,9 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.smol_csum_batch_emit_fields.restype = i32
         L.smol_csum_apply_fields.argtypes = [vp, u32, ctypes.POINTER(FieldsC)]
         L.smol_csum_apply_fields.restype = i32
+    if hasattr(L, "smol_csum_batch_verify_copy"):
+        L.smol_csum_batch_verify_copy.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps), vp, vp, vp, vp, vp]
+        L.smol_csum_batch_verify_copy.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []
@@ -196,6 +223,7 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         "smol_csum_tool_form": ([i32, i32, ctypes.POINTER(i32)], i32),
         "smol_csum_tool_set_fields_kernel": ([vp, i32], i32),
         "smol_csum_tool_walk_launch": ([i32, i32, i32, i32, i32, ctypes.POINTER(i32)], i32),
+        "smol_csum_tool_set_vcopy_stores": ([vp, i32], i32),
     }
     assert set(optional) == set(OPTIONAL_TOOL_SYMBOLS)
     for name in OPTIONAL_TOOL_SYMBOLS:

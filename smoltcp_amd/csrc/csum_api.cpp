@@ -46,6 +46,7 @@ struct smol_csum_ctx {
     int desc_staged;          // 1: the staged form (also before any sample), 0: in place
     uint32_t since_probe;
     int fields_kernel;        // emit_fields: FK_AUTO, or a forced form (smol_csum_tool_set_fields_kernel)
+    bool vcopy_nt;            // verify_copy: non-temporal body stores (smol_csum_tool_set_vcopy_stores)
 };
 
 namespace {
@@ -329,6 +330,7 @@ int smol_csum_ctx_create(int device, smol_csum_ctx_t** out) {
     c->desc_staged = 1;
     c->since_probe = 0;
     c->fields_kernel = FK_AUTO;
+    c->vcopy_nt = false;
     c->tile_records = 32;
     c->max_blocks_set = false;
     c->xcd_remap = -1;
@@ -438,6 +440,46 @@ int smol_csum_batch_emit_fields(smol_csum_ctx_t* ctx, const uint8_t* d_buf, cons
                 break;
         }
         if (e != hipSuccess) return hip_fail(e, "emit_fields kernel launch");
+    }
+    return SMOL_OK;
+}
+
+// Verify with the payloads delivered in the same pass (include/smolcsum.h).  Uses none of the context's
+// scratch or events, so calls on different streams are independent.
+int smol_csum_batch_verify_copy(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
+                                const smol_checksum_caps_t* caps, uint8_t* d_dst, const smol_csum_slot_t* d_slots,
+                                uint8_t* d_status, smol_csum_span_t* d_spans, void* stream) {
+    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
+    int rc = check_batch(b, d_buf);
+    if (rc != SMOL_OK || b->n == 0) return rc;
+    if (!d_dst || !d_slots || !d_status || !d_spans || ((uintptr_t)d_slots & 15u) != 0 || ((uintptr_t)d_spans & 7u) != 0)
+        return SMOL_EINVAL;
+    KParams p;
+    std::memset(&p, 0, sizeof p);
+    p.buf = const_cast<uint8_t*>(d_buf);  // (only read)
+    p.stride = b->stride;
+    p.len = b->len;
+    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
+    p.caps_ipv4 = caps->ipv4;
+    p.caps_udp = caps->udp;
+    p.caps_tcp = caps->tcp;
+    p.caps_icmpv4 = caps->icmpv4;
+    p.caps_icmpv6 = caps->icmpv6;
+    p.dummy = ctx->dummy;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
+    const hipStream_t s = (hipStream_t)stream;
+    const int shape = ctx->shape >= 0 ? ctx->shape : vcopy_shape(b->len, b->desc != nullptr);
+    // launch_records: consecutive launches, the per-record arrays advancing with the records
+    const uint64_t per = ctx->launch_records && ctx->launch_records < b->n ? ctx->launch_records : b->n;
+    for (uint64_t i0 = 0; i0 < b->n; i0 += per) {
+        p.n = b->n - i0 < per ? b->n - i0 : per;
+        p.desc = b->desc ? b->desc + i0 : nullptr;
+        if (!b->desc) p.buf = const_cast<uint8_t*>(d_buf) + i0 * b->stride;
+        p.status = d_status + i0;
+        const VCopyArgs v = {d_dst, d_slots + i0, d_spans + i0};
+        const hipError_t e = launch_vcopy(shape, ctx->vcopy_nt, p, v, ctx->max_blocks, s);
+        if (e != hipSuccess) return hip_fail(e, "verify_copy kernel launch");
     }
     return SMOL_OK;
 }
@@ -582,6 +624,12 @@ int smol_csum_tool_set_launch_records(smol_csum_ctx_t* ctx, uint64_t records) {
 int smol_csum_tool_set_fields_kernel(smol_csum_ctx_t* ctx, int kernel) {
     if (!ctx || kernel < FK_AUTO || kernel > FK_DWALK) return SMOL_EINVAL;
     ctx->fields_kernel = kernel;
+    return SMOL_OK;
+}
+
+int smol_csum_tool_set_vcopy_stores(smol_csum_ctx_t* ctx, int nt) {
+    if (!ctx || (nt != 0 && nt != 1)) return SMOL_EINVAL;
+    ctx->vcopy_nt = nt == 1;
     return SMOL_OK;
 }
 

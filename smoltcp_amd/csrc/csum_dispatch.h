@@ -220,6 +220,15 @@ inline int pick_fields(int forced, const smol_csum_batch_t* b, const KParams& p)
     return d_ok ? FK_DWALK : FK_WALK;
 }
 
+// ---- verify_copy (smol_csum_batch_verify_copy) -----------------------------------------------------
+// One kernel outside the registry (csum_vcopy.hip); its launch shape, on the 16-byte grid.  Measured
+// (tools/exp_verify_copy.py, profiles/verify_copy_kernels.json): descriptor batches 8 x 7 (C3 2.25 ms
+// against 8 x 6's 2.38 and 16 x 4's 2.47; 16 x 3 2.77 in an earlier call).
+inline int vcopy_shape(uint32_t len, bool has_desc) {
+    if (has_desc) return CFG_G8U7;
+    return auto_shape(len, false, kWalkEmitDesc);
+}
+
 inline Pick pick_kernel(const PickCtx& ctx, int mode, const smol_csum_batch_t* b, const KParams& p) {
     const bool has_desc = b->desc != nullptr;
     const bool nhc = p.addrs != nullptr;

@@ -174,9 +174,11 @@ __device__ inline uint64_t logical_block(uint32_t xcd_remap) {
 // | G << 8 | U (smol_csum_tool_last_launch): tests check that a forced variant runs the kernel it
 // names rather than a dispatch fallback.
 // KERN_*_FIELDS: the three forms of smol_csum_batch_emit_fields (variant 0; they have no registry row).
+// KERN_VCOPY: smol_csum_batch_verify_copy's kernel (no registry row either; variant 0 plain body stores, 1
+// non-temporal ones).
 enum {
     KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6,
-    KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9
+    KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9, KERN_VCOPY = 10
 };
 inline std::atomic<uint32_t> g_last_launch{0};
 inline void note_launch(uint32_t kern, uint32_t var, uint32_t g, uint32_t u) {
@@ -229,6 +231,17 @@ template <bool IMPLICIT>
 hipError_t launch_walk_fields(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s);
 hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s);
 hipError_t launch_dwalk_fields(const KParams& p, hipStream_t s);
+
+// verify_copy (smol_csum_batch_verify_copy, csum_vcopy.hip): verify's parse, sums and gates, and each
+// record's L4 payload delivered to its slot of `dst` in the same pass.  Outside the variant registry.
+struct VCopyArgs {
+    uint8_t* dst;
+    const smol_csum_slot_t* slots;  // one 16-B entry per record (input)
+    smol_csum_span_t* spans;        // one 8-B entry per record (output)
+};
+// `nt`: body chunks stored non-temporal instead of with the default cache policy (measurements).
+hipError_t launch_vcopy(int shape, bool nt, const KParams& p, const VCopyArgs& v, uint32_t max_blocks,
+                        hipStream_t s);
 
 // Synthetic batches and fault injection (tools; include/smolcsum_tools.h).
 struct SynthParams {

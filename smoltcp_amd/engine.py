@@ -16,7 +16,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import NO_FIELD, BatchC, Caps, FieldsC, check, lib
+from ._lib import NO_FIELD, BatchC, Caps, FieldsC, SlotC, SpanC, check, lib
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -52,6 +52,22 @@ MAX_FRAGMENTS = 256
 # smol_csum_fields_t: one record's emit result (smol_csum_batch_emit_fields)
 FIELDS_DTYPE = np.dtype([("off", "<u2", (3,)), ("val", "<u2", (3,)), ("status", "u1"), ("reserved", "u1", (3,))])
 assert FIELDS_DTYPE.itemsize == 16 == ctypes.sizeof(FieldsC)
+
+
+# smol_csum_slot_t / smol_csum_span_t: a record's destination slot and payload span (smol_csum_batch_verify_copy)
+SLOT_DTYPE = np.dtype([("dst_offset", "<u8"), ("cap", "<u4"), ("reserved", "<u4")])
+assert SLOT_DTYPE.itemsize == 16 == ctypes.sizeof(SlotC)
+SPAN_DTYPE = np.dtype([("len", "<u4"), ("off", "<u2"), ("copied", "u1"), ("reserved", "u1")])
+assert SPAN_DTYPE.itemsize == 8 == ctypes.sizeof(SpanC)
+
+
+def make_slots(dst_offsets, caps) -> np.ndarray:
+    """Host array of smol_csum_slot_t (view it as uint8 and copy it to the device)."""
+    n = len(dst_offsets)
+    s = np.zeros(n, dtype=SLOT_DTYPE)
+    s["dst_offset"] = np.asarray(dst_offsets, dtype=np.uint64)
+    s["cap"] = np.broadcast_to(np.asarray(caps, dtype=np.uint32), (n,))
+    return s
 
 
 def apply_fields(host_buf: np.ndarray, record_offsets, record_lens, fields) -> np.ndarray:
@@ -331,6 +347,31 @@ class ChecksumEngine:
               "smol_csum_batch_verify")
         return status
 
+    def verify_copy(self, buf, batch: Batch, dst, slots, caps=None, status=None, spans=None, stream=None):
+        """Verify, and in the same pass deliver every record's UDP / TCP payload to its slot of `dst`
+        (smol_csum_batch_verify_copy).  `slots`: a device uint8 tensor of n smol_csum_slot_t (see
+        make_slots); `dst`: the destination uint8 device tensor, written only inside the copied ranges.
+        Returns (status, spans): verify's status bytes and an n x 8 uint8 device tensor of
+        smol_csum_span_t (view its host copy as SPAN_DTYPE).  The copy does not wait for the verdict:
+        commit a slot only when its status byte has ST_ACCEPT."""
+        import torch
+
+        self._check_buf(buf, batch)
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert slots.is_cuda and slots.is_contiguous() and slots.numel() * slots.dtype.itemsize >= 16 * batch.n
+        if status is None:
+            status = torch.empty(batch.n, dtype=torch.uint8, device=buf.device)
+        if spans is None:
+            spans = torch.empty((batch.n, 8), dtype=torch.uint8, device=buf.device)
+        assert spans.is_cuda and spans.is_contiguous() and spans.numel() * spans.dtype.itemsize >= 8 * batch.n
+        b = batch.c()
+        c = _caps(caps)
+        check(self._L.smol_csum_batch_verify_copy(self._h, buf.data_ptr(), ctypes.byref(b), ctypes.byref(c),
+                                                dst.data_ptr(), slots.data_ptr(), status.data_ptr(),
+                                                spans.data_ptr(), self._stream(stream)),
+              "smol_csum_batch_verify_copy")
+        return status, spans
+
     # ---- tooling ----
     def synth(self, buf, batch: Batch, profile: int, seed: int, stream=None):
         self._check_buf(buf, batch)
@@ -400,6 +441,10 @@ class ChecksumEngine:
         3 the descriptor walk (a form that does not serve the batch gives way to the walk kernel)."""
         check(self._L.smol_csum_tool_set_fields_kernel(self._h, int(kernel)), "smol_csum_tool_set_fields_kernel")
 
+    def set_vcopy_stores(self, nt: bool):
+        """verify_copy's body stores: False the library's choice (the default cache policy), True non-temporal."""
+        check(self._L.smol_csum_tool_set_vcopy_stores(self._h, int(bool(nt))), "smol_csum_tool_set_vcopy_stores")
+
     def set_tile(self, records: int):
         check(self._L.smol_csum_tool_set_tile(self._h, int(records)), "smol_csum_tool_set_tile")
 
@@ -424,12 +469,12 @@ class ChecksumEngine:
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
         "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
-        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)", "variant": VAR, "G":
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
-                 6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)"}
+                 6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

@@ -219,6 +219,19 @@ public:
         check(smol_csum_batch_verify(ctx_, d_buf, &bc, &cc, d_status, stream), "smol_csum_batch_verify");
     }
 
+    // verify, and in the same pass every record's UDP / TCP payload delivered to d_dst at d_slots[i]
+    // (UdpPacket::payload udp.rs:153-157 / TcpPacket::payload tcp.rs:419-423, the copy of
+    // socket/udp.rs:522-523 and socket/tcp.rs:2231); d_spans[i] = the span and whether it was copied.  The
+    // copy does not wait for the verdict: commit a slot only when d_status[i] & SMOL_ST_ACCEPT.
+    void verify_copy(const uint8_t* d_buf, const Batch& b, uint8_t* d_dst, const smol_csum_slot_t* d_slots,
+                     uint8_t* d_status, smol_csum_span_t* d_spans,
+                     const smoltcp::phy::ChecksumCapabilities& caps = {}, void* stream = nullptr) {
+        auto bc = b.c();
+        auto cc = caps.c();
+        check(smol_csum_batch_verify_copy(ctx_, d_buf, &bc, &cc, d_dst, d_slots, d_status, d_spans, stream),
+              "smol_csum_batch_verify_copy");
+    }
+
     // IPv4 fragment groups: d_groups[k] = one datagram's fragments (consecutive records).  Fills every
     // fragment header and each datagram's L4 checksum over its reassembled payload (the iface's
     // "emit whole, then fragment", src/iface/interface/mod.rs:1276-1331).
