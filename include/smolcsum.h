@@ -27,6 +27,8 @@
  *         who patches them there with smol_csum_apply_fields;
  *       - smol_csum_batch_verify_copy == verify, and in the same pass the UDP / TCP payloads
  *         delivered to caller-chosen slots of a second device buffer (the socket's rx_buffer copy);
+ *       - smol_csum_batch_verify_reassemble == verify over IPv4 fragment groups, and in the same pass
+ *         the fragment payloads put together in the datagram's slot (the reassembler's copy);
  *       - smol_csum_batch_data   == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
@@ -349,7 +351,8 @@ typedef struct {
  *
  * SMOL_EINVAL: NULL ctx, bad caps, NULL d_dst / d_slots / d_status / d_spans with n > 0, d_slots
  * not 16-byte aligned, d_spans not 8-byte aligned.  SMOL_ERANGE: as verify.  n == 0 returns SMOL_OK
- * and launches nothing.  Not covered: IPv4 fragment groups and the 6LoWPAN NHC entry points.
+ * and launches nothing.  Not covered: the 6LoWPAN NHC entry points.  IPv4 fragment groups have their
+ * own call, smol_csum_batch_verify_reassemble (section 3).
  *
  * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive, as emit_fields was). */
 int smol_csum_batch_verify_copy(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
@@ -416,6 +419,78 @@ int smol_csum_batch_emit_frag(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_c
 int smol_csum_batch_verify_frag(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
                                 const smol_csum_frag_group_t* d_groups, uint64_t n_groups,
                                 const smol_checksum_caps_t* caps, uint8_t* d_status, void* stream);
+
+/* One reassembled datagram (16 bytes, 16-byte-aligned device array, output; one per group). */
+typedef struct {
+    uint32_t len;      /* reassembled IPv4 payload bytes T (0: the group is not usable)        */
+    uint32_t l4_len;   /* L4 payload bytes inside it (UDP length - 8; TCP T - 4*data offset)    */
+    uint16_t l4_off;   /* datagram-relative offset of the L4 payload (UDP 8, TCP 4*data offset);
+                          0 with l4_len 0: no UDP/TCP payload span                             */
+    uint8_t protocol;  /* the IPv4 protocol byte of the reassembly key (0 when not usable)      */
+    uint8_t copied;    /* 1: len <= cap and bytes [0, len) were delivered                       */
+    uint32_t reserved; /* 0 */
+} smol_csum_dgram_t;
+
+/* verify_frag, and every group's fragment payloads delivered to their places in the datagram's slot of
+ * d_dst, in one pass over the fragments.  On receive the reference reads a fragmented datagram twice:
+ * PacketAssembler::add copies each fragment's payload into the assembler's buffer
+ * (src/iface/fragmentation.rs:139-151, called from src/iface/interface/ipv4.rs:131), and once
+ * assemble() returns the whole payload (ipv4.rs:136) the L4 Repr::parse sums all of it
+ * (udp.rs:250-257, tcp.rs:917-919, icmpv4.rs:404-407).  Here each payload byte is read once.  The
+ * reassembler's bookkeeping (keys, timeouts, holes) stays with the caller, who forms the groups; this
+ * call serves its copy.
+ *
+ * Status.  d_status (one byte per RECORD) holds exactly the bytes smol_csum_batch_verify_frag writes for
+ * the same batch, groups and caps.  Records outside every group are not written; records of an invalid
+ * group are neither read nor written.
+ *
+ * Reassembly.  d_slots and d_dgrams have one entry per GROUP.  A group is usable under the contract
+ * above: every record passes Ipv4Packet::check_len, all share one reassembly key, the payloads cover
+ * [0, T) exactly once, exactly one last fragment ends at T.  For a usable group len = T and protocol is
+ * the key's protocol byte; when T <= cap, fragment j's payload is written to
+ * d_dst[dst_offset + start_j .. dst_offset + end_j) and copied = 1 (PacketAssembler::add's
+ * buffer[offset..][..len].copy_from_slice(data)).  This holds whatever the protocol and whatever the L4
+ * verdict, as the reference reassembles before it looks at L4 (ipv4.rs:111-143): a raw socket's
+ * datagram (SMOL_REC_IPHDR_ONLY on any record) is delivered, a protocol smoltcp does not checksum is
+ * delivered with status SMOL_ST_UNSUPPORTED, and a datagram whose L4 check_len fails (a UDP length field
+ * above T, a port-0 rejection) is delivered whole with status SMOL_ST_MALFORMED and l4_off = l4_len = 0.
+ * A group of one unfragmented packet delivers that packet's IP payload.  When T > cap nothing is stored,
+ * copied = 0 and len = T is still reported, so the caller can size a retry.  A group that is not usable
+ * stores nothing and its entry is all zero; so is the entry of an invalid group (first >= n, count 0 or
+ * above SMOL_MAX_FRAGMENTS, count > n - first, reserved != 0): the entry is indexed by group, no record
+ * is touched.
+ *
+ * L4 span.  l4_off / l4_len are defined when the datagram reaches the UDP or TCP gate and is neither
+ * SMOL_ST_MALFORMED nor SMOL_ST_UNSUPPORTED: the spans smol_csum_batch_verify_copy reports, relative to
+ * the datagram start (UdpPacket::payload, udp.rs:153-157; TcpPacket::payload, tcp.rs:419-423).  For
+ * UDP the sum covers [0, UDP length) while the copy always covers [0, T): bytes past the UDP length
+ * are delivered and not summed, as in the reference's two passes.
+ *
+ * THE COPY DOES NOT WAIT FOR THE VERDICT, neither the L4 checksum's nor a fragment's IPv4 header
+ * gate's.  The caller commits a slot only when every status byte of the group has SMOL_ST_ACCEPT.
+ *
+ * Writes.  No byte of d_dst is ever read and none outside [dst_offset, dst_offset + T) of a delivered
+ * group is ever written.  The first and last piece of every fragment's range go out as byte-masked
+ * stores, never read-modify-write: two fragments of a datagram meet at a multiple of 8, which can fall
+ * inside one 16-byte destination chunk written by two wavefronts.  Slots may lie back to back at any
+ * alignment; they must not overlap each other or the batch.  d_buf is only read, and only in 16-byte
+ * chunks that hold at least one byte of a record.
+ *
+ * Resources.  No context scratch, no event, no allocation; stream-ordered on `stream`, and calls on
+ * different streams are independent (also on one context).
+ *
+ * SMOL_EINVAL: NULL ctx, bad caps, NULL d_groups / d_dst / d_slots / d_status / d_dgrams with
+ * n_groups > 0, d_groups, d_slots or d_dgrams not 16-byte aligned.  SMOL_ERANGE: as verify_frag.
+ * n_groups == 0 returns SMOL_OK and launches nothing.
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive, as verify_copy was). */
+int smol_csum_batch_verify_reassemble(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
+                                      const smol_csum_frag_group_t* d_groups, uint64_t n_groups,
+                                      const smol_checksum_caps_t* caps, uint8_t* d_dst,
+                                      const smol_csum_slot_t* d_slots, /* one per GROUP */
+                                      uint8_t* d_status,               /* one per RECORD, as verify_frag */
+                                      smol_csum_dgram_t* d_dgrams,     /* one per GROUP */
+                                      void* stream);
 
 /* ---- 4. 6LoWPAN next-header-compressed UDP (RFC 6282 §4.3) ------------------------------- */
 

@@ -33,7 +33,7 @@ ABI_SYMBOLS = [
     "smol_csum_batch_verify", "smol_csum_batch_copy_emit", "smol_csum_batch_emit_fields",
     "smol_csum_batch_verify_copy",
     "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
-    "smol_csum_batch_verify_frag", "smol_csum_batch_nhc_udp_emit",
+    "smol_csum_batch_verify_frag", "smol_csum_batch_verify_reassemble", "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
 ]
 TOOL_SYMBOLS = [
@@ -125,6 +125,19 @@ class SpanC(ctypes.Structure):
     ]
 
 
+class DgramC(ctypes.Structure):
+    """smol_csum_dgram_t: one reassembled datagram (smol_csum_batch_verify_reassemble)."""
+
+    _fields_ = [
+        ("len", ctypes.c_uint32),
+        ("l4_len", ctypes.c_uint32),
+        ("l4_off", ctypes.c_uint16),
+        ("protocol", ctypes.c_uint8),
+        ("copied", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint32),
+    ]
+
+
 _LIBS = {}
 
 
@@ -180,6 +193,10 @@ def lib(path: str | None = None) -> ctypes.CDLL:
     if hasattr(L, "smol_csum_batch_verify_copy"):
         L.smol_csum_batch_verify_copy.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps), vp, vp, vp, vp, vp]
         L.smol_csum_batch_verify_copy.restype = i32
+    if hasattr(L, "smol_csum_batch_verify_reassemble"):
+        L.smol_csum_batch_verify_reassemble.argtypes = [vp, vp, ctypes.POINTER(BatchC), vp, u64, ctypes.POINTER(Caps),
+                                                        vp, vp, vp, vp, vp]
+        L.smol_csum_batch_verify_reassemble.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []

@@ -528,6 +528,42 @@ int smol_csum_batch_verify_frag(smol_csum_ctx_t* ctx, const uint8_t* d_buf, cons
     return run_frag(ctx, MODE_VERIFY, const_cast<uint8_t*>(d_buf), b, d_groups, n_groups, caps, d_status, stream);
 }
 
+// verify_frag with the fragment payloads put together in each group's slot in the same pass
+// (include/smolcsum.h).  Uses none of the context's scratch or events, so calls on different streams are
+// independent.
+int smol_csum_batch_verify_reassemble(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
+                                      const smol_csum_frag_group_t* d_groups, uint64_t n_groups,
+                                      const smol_checksum_caps_t* caps, uint8_t* d_dst, const smol_csum_slot_t* d_slots,
+                                      uint8_t* d_status, smol_csum_dgram_t* d_dgrams, void* stream) {
+    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
+    int rc = check_batch(b, d_buf);
+    if (rc != SMOL_OK) return rc;
+    if (n_groups == 0) return SMOL_OK;
+    if (b->n == 0 || !d_groups || ((uintptr_t)d_groups & 15u) != 0) return SMOL_EINVAL;
+    if (!d_dst || !d_slots || !d_status || !d_dgrams || ((uintptr_t)d_slots & 15u) != 0 || ((uintptr_t)d_dgrams & 15u) != 0)
+        return SMOL_EINVAL;
+    KParams p;
+    std::memset(&p, 0, sizeof p);
+    p.buf = const_cast<uint8_t*>(d_buf);  // (only read)
+    p.desc = b->desc;
+    p.n = b->n;
+    p.stride = b->stride;
+    p.len = b->len;
+    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
+    p.caps_ipv4 = caps->ipv4;
+    p.caps_udp = caps->udp;
+    p.caps_tcp = caps->tcp;
+    p.caps_icmpv4 = caps->icmpv4;
+    p.caps_icmpv6 = caps->icmpv6;
+    p.status = d_status;
+    p.dummy = ctx->dummy;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
+    const FragCopyArgs v = {d_dst, d_slots, d_dgrams};
+    const hipError_t e = launch_fragcopy(p, d_groups, n_groups, v, (hipStream_t)stream);
+    return e == hipSuccess ? SMOL_OK : hip_fail(e, "verify_reassemble kernel launch");
+}
+
 // ---- 6LoWPAN NHC UDP --------------------------------------------------------------------------
 
 int smol_csum_batch_nhc_udp_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,

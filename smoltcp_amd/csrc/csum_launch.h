@@ -176,9 +176,11 @@ __device__ inline uint64_t logical_block(uint32_t xcd_remap) {
 // KERN_*_FIELDS: the three forms of smol_csum_batch_emit_fields (variant 0; they have no registry row).
 // KERN_VCOPY: smol_csum_batch_verify_copy's kernel (no registry row either; variant 0 plain body stores, 1
 // non-temporal ones).
+// KERN_FRAGCOPY: smol_csum_batch_verify_reassemble's kernel (no registry row; variant 0, G 64, U its chunks per lane).
 enum {
     KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6,
-    KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9, KERN_VCOPY = 10
+    KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9, KERN_VCOPY = 10,
+    KERN_FRAGCOPY = 11
 };
 inline std::atomic<uint32_t> g_last_launch{0};
 inline void note_launch(uint32_t kern, uint32_t var, uint32_t g, uint32_t u) {
@@ -258,6 +260,16 @@ hipError_t launch_corrupt(const SynthParams& p, uint32_t every, hipStream_t s);
 // IPv4 fragment groups (csum_frag.hip): MODE_EMIT / MODE_VERIFY, one wavefront per group.
 hipError_t launch_frag(int mode, const KParams& p, const smol_csum_frag_group_t* groups, uint64_t ngroups,
                        hipStream_t s);
+// verify_reassemble (smol_csum_batch_verify_reassemble, csum_fragcopy.hip): verify_frag's status bytes, and
+// every usable group's fragment payloads delivered to the group's slot of `dst` in the same pass.  One
+// 256-thread workgroup per group; outside the variant registry.
+struct FragCopyArgs {
+    uint8_t* dst;
+    const smol_csum_slot_t* slots;  // one 16-B entry per group (input)
+    smol_csum_dgram_t* dgrams;      // one 16-B entry per group (output)
+};
+hipError_t launch_fragcopy(const KParams& p, const smol_csum_frag_group_t* groups, uint64_t ngroups,
+                           const FragCopyArgs& v, hipStream_t s);
 hipError_t launch_stream_read(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t max_blocks,
                               hipStream_t s);
 hipError_t launch_field_probe(uint8_t* buf, uint64_t bytes, uint64_t stride, uint32_t f1, uint32_t f2,

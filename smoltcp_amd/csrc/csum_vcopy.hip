@@ -34,32 +34,7 @@ namespace vcopy {
 
 constexpr int WIN = 128;  // the header window: 16-B grid, Grid<false>
 constexpr int WIN_CH = WIN / 16;
-
-// The chunk the next lane of the group holds (lane G - 1: lane 0's).
-template <int G>
-__device__ __forceinline__ u32x4 next4(const u32x4& c, int lane) {
-    u32x4 n;
-    n.x = group_next<G>(c.x, lane);
-    n.y = group_next<G>(c.y, lane);
-    n.z = group_next<G>(c.z, lane);
-    n.w = group_next<G>(c.w, lane);
-    return n;
-}
-
-// Aligned-word sum of the chunk's bytes inside the record span [0, s1) (pos: chunk start relative to
-// the record start), as verify sums them.
-__device__ __forceinline__ uint32_t sum_chunk(const u32x4& c, int pos, int s1, uint32_t acc) {
-    if (pos >= s1 || pos + 16 <= 0) return acc;
-    if (pos < 0 || pos + 16 > s1) return sum_masked_words(c, -pos, s1 - pos, acc);
-    return add_words(c.x, add_words(c.y, add_words(c.z, add_words(c.w, acc))));
-}
-
-// Store the bytes [lo, hi) of chunk c (chunk-relative) at the 16-B aligned dst: nothing is read back.
-__device__ __forceinline__ void store_edge(gu8 dst, const u32x4& c, int lo, int hi) {
-    const uint32_t cw[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) store_dword_masked(dst + 4 * i, cw[i], byte_mask(lo, hi, i));
-}
+// next4, sum_chunk, store_edge: csum_walk.h (shared with csum_fragcopy.hip)
 
 }  // namespace vcopy
 

@@ -16,7 +16,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import NO_FIELD, BatchC, Caps, FieldsC, SlotC, SpanC, check, lib
+from ._lib import NO_FIELD, BatchC, Caps, DgramC, FieldsC, SlotC, SpanC, check, lib
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -59,6 +59,10 @@ SLOT_DTYPE = np.dtype([("dst_offset", "<u8"), ("cap", "<u4"), ("reserved", "<u4"
 assert SLOT_DTYPE.itemsize == 16 == ctypes.sizeof(SlotC)
 SPAN_DTYPE = np.dtype([("len", "<u4"), ("off", "<u2"), ("copied", "u1"), ("reserved", "u1")])
 assert SPAN_DTYPE.itemsize == 8 == ctypes.sizeof(SpanC)
+# smol_csum_dgram_t: one reassembled datagram per fragment group (smol_csum_batch_verify_reassemble)
+DGRAM_DTYPE = np.dtype([("len", "<u4"), ("l4_len", "<u4"), ("l4_off", "<u2"), ("protocol", "u1"), ("copied", "u1"),
+                        ("reserved", "<u4")])
+assert DGRAM_DTYPE.itemsize == 16 == ctypes.sizeof(DgramC)
 
 
 def make_slots(dst_offsets, caps) -> np.ndarray:
@@ -306,6 +310,34 @@ class ChecksumEngine:
                                                 self._stream(stream)), "smol_csum_batch_verify_frag")
         return status
 
+    def verify_reassemble(self, buf, batch: Batch, groups, dst, slots, caps=None, status=None, dgrams=None, stream=None):
+        """verify_frag, and in the same pass every usable group's fragment payloads put together in the
+        group's slot of `dst` (smol_csum_batch_verify_reassemble).  `groups`: as verify_frag; `slots`: a
+        device uint8 tensor of one smol_csum_slot_t per GROUP (see make_slots); `dst`: the destination uint8
+        device tensor, written only inside the delivered datagrams.  Returns (status, dgrams): verify_frag's
+        status bytes (one per record; a fresh tensor starts zeroed) and an n_groups x 16 uint8 device tensor
+        of smol_csum_dgram_t (view its host copy as DGRAM_DTYPE).  The copy does not wait for the verdict:
+        commit a slot only when every status byte of its group has ST_ACCEPT."""
+        import torch
+
+        self._check_buf(buf, batch)
+        assert groups.is_cuda and groups.numel() % 16 == 0
+        ng = groups.numel() // 16
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert slots.is_cuda and slots.is_contiguous() and slots.numel() * slots.dtype.itemsize >= 16 * ng
+        if status is None:
+            status = torch.zeros(batch.n, dtype=torch.uint8, device=buf.device)
+        if dgrams is None:
+            dgrams = torch.empty((ng, 16), dtype=torch.uint8, device=buf.device)
+        assert dgrams.is_cuda and dgrams.is_contiguous() and dgrams.numel() * dgrams.dtype.itemsize >= 16 * ng
+        b = batch.c()
+        c = _caps(caps)
+        check(self._L.smol_csum_batch_verify_reassemble(self._h, buf.data_ptr(), ctypes.byref(b), groups.data_ptr(), ng,
+                                                      ctypes.byref(c), dst.data_ptr(), slots.data_ptr(),
+                                                      status.data_ptr(), dgrams.data_ptr(), self._stream(stream)),
+              "smol_csum_batch_verify_reassemble")
+        return status, dgrams
+
     def nhc_udp_emit(self, buf, batch: Batch, addrs, caps=None, status=None, stream=None):
         """6LoWPAN NHC UDP emit (smol_csum_batch_nhc_udp_emit): ``addrs`` is a device uint8 tensor of
         n x 32 bytes (IPv6 source, destination per record)."""
@@ -469,12 +501,13 @@ class ChecksumEngine:
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
         "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
-        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel", "variant": VAR, "G":
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
-                 6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel"}
+                 6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel",
+                 11: "fragcopy_kernel"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

@@ -252,6 +252,21 @@ public:
         check(smol_csum_batch_verify_frag(ctx_, d_buf, &bc, d_groups, n_groups, &cc, d_status, stream),
               "smol_csum_batch_verify_frag");
     }
+    // verify_frag, and in the same pass every usable group's fragment payloads put together at d_slots[k] of
+    // d_dst (PacketAssembler::add's copy, src/iface/fragmentation.rs:139-151); d_dgrams[k] = the datagram's
+    // length, protocol, L4 payload span and whether it was copied.  d_slots / d_dgrams: one per GROUP,
+    // d_status: one per record.  The copy waits for no verdict: commit a slot only when every status byte of
+    // its group has SMOL_ST_ACCEPT.
+    void verify_reassemble(const uint8_t* d_buf, const Batch& b, const smol_csum_frag_group_t* d_groups,
+                           uint64_t n_groups, uint8_t* d_dst, const smol_csum_slot_t* d_slots, uint8_t* d_status,
+                           smol_csum_dgram_t* d_dgrams, const smoltcp::phy::ChecksumCapabilities& caps = {},
+                           void* stream = nullptr) {
+        auto bc = b.c();
+        auto cc = caps.c();
+        check(smol_csum_batch_verify_reassemble(ctx_, d_buf, &bc, d_groups, n_groups, &cc, d_dst, d_slots, d_status,
+                                                d_dgrams, stream),
+              "smol_csum_batch_verify_reassemble");
+    }
 
     // 6LoWPAN NHC UDP (sixlowpan::nhc::UdpNhcRepr::emit / ::parse): every record is a LOWPAN_NHC
     // UDP packet; d_addrs[i] holds record i's IPv6 addresses (IPHC-decompressed).
