@@ -29,6 +29,8 @@
  *         delivered to caller-chosen slots of a second device buffer (the socket's rx_buffer copy);
  *       - smol_csum_batch_verify_reassemble == verify over IPv4 fragment groups, and in the same pass
  *         the fragment payloads put together in the datagram's slot (the reassembler's copy);
+ *       - smol_csum_batch_fragment_emit == emit over whole IPv4 datagrams, and in the same pass each
+ *         datagram cut into the frames the iface sends (dispatch_ip's and dispatch_ipv4_frag's copy);
  *       - smol_csum_batch_data   == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
@@ -491,6 +493,85 @@ int smol_csum_batch_verify_reassemble(smol_csum_ctx_t* ctx, const uint8_t* d_buf
                                       uint8_t* d_status,               /* one per RECORD, as verify_frag */
                                       smol_csum_dgram_t* d_dgrams,     /* one per GROUP */
                                       void* stream);
+
+/* Where and how one datagram is cut (16 bytes, 16-byte-aligned device array, input; one per record). */
+typedef struct {
+    uint64_t dst_offset; /* byte offset of the datagram's first frame in d_dst (any alignment) */
+    uint32_t cap;        /* bytes available there                                                */
+    uint16_t ip_mtu;     /* DeviceCapabilities::ip_mtu() for this datagram (phy/mod.rs:282-293)  */
+    uint16_t ident;      /* the iface's ipv4_id, written into every fragment (mod.rs:1323-1324)  */
+} smol_csum_fragplan_t;
+
+/* What became of one datagram (16 bytes, 16-byte-aligned device array, output; one per record). */
+typedef struct {
+    uint32_t count;     /* frames the datagram makes (0: not an IPv4 datagram this call cuts)     */
+    uint32_t frame_len; /* bytes of every frame but the last: io + 20 + step                      */
+    uint32_t last_len;  /* bytes of the last frame (count == 1: the only one)                     */
+    uint8_t status;     /* the byte smol_csum_batch_emit puts in d_status for the record          */
+    uint8_t written;    /* 1: all count frames were stored                                        */
+    uint16_t reserved;  /* 0 */
+} smol_csum_fragout_t;
+
+/* emit, and every whole IPv4 datagram cut into the frames the iface sends, in one pass over the datagram:
+ * the mirror of smol_csum_batch_verify_reassemble, whose input this call's output is.  On transmit the
+ * reference reads a datagram larger than the IP MTU twice: it emits it whole into frag.buffer, the L4
+ * fill_checksum summing every byte (src/iface/interface/mod.rs:1263-1331), and then copies it out a
+ * fragment at a time into the TX token buffers, each behind a fresh IPv4 header with its own header
+ * checksum and, on Ethernet, a fresh Ethernet header (mod.rs:1334-1347 for the first fragment,
+ * dispatch_ipv4_frag, src/iface/interface/ipv4.rs:421-482, for the rest).  Here each datagram byte is read
+ * once and each frame byte written once.
+ *
+ * Records.  Each record of the batch (fixed-stride or descriptors) is one whole IPv4 datagram,
+ * SMOL_KIND_IP or SMOL_KIND_ETH (ethertype 0x0800); io below is 0 for SMOL_KIND_IP and 14 for
+ * SMOL_KIND_ETH.  d_buf is only read, and only in 16-byte chunks that hold at least one byte of a record.
+ *
+ * Which records are cut.  A record is cut when it carries an IPv4 header that passes
+ * Ipv4Packet::check_len, its IHL is 5 (Ipv4Repr::emit writes no options), it is not itself a fragment
+ * (MF clear and offset 0), and ip_mtu >= 28.  Every other record (IPv6: smoltcp has no IPv6
+ * fragmentation; a non-IP ethertype; SMOL_KIND_RAW) gets count = 0, written = 0 and nothing stored.
+ * status is always the byte smol_csum_batch_emit would report for the record.
+ *
+ * Cut.  T = total length - 20; step = (ip_mtu - 20) - (ip_mtu - 20) % 8 (max_ipv4_fragment_size,
+ * phy/mod.rs:297-300); S = frame_stride, or frame_len when frame_stride == 0; frame k starts at
+ * d_dst + dst_offset + k * S.
+ *   - 20 + T <= ip_mtu: the datagram goes out as one frame, as the iface sends it (mod.rs:1276):
+ *     count = 1, frame_len = last_len = io + 20 + T; the frame is the record's first io + 20 + T bytes
+ *     with emit's fields, its ident, DF and flags as the caller wrote them.
+ *   - otherwise count = ceil(T / step), frame_len = io + 20 + step, and frame k is the record's io
+ *     Ethernet bytes, the 20-byte header, then payload bytes [k * step, min((k + 1) * step, T)).  The
+ *     header is the datagram's with total length (20 + the payload length), ident (the plan's), DF
+ *     cleared, MF set on all frames but the last, fragment offset k * step / 8 and the header checksum
+ *     (filled under caps.ipv4.tx(), else 0) rewritten.
+ *
+ * Checksums.  The payload bytes delivered are those smol_csum_batch_emit would leave in the record under
+ * caps: the L4 checksum over the whole datagram (0 without tx(); UDP 0 mapped to 0xffff; IGMP always
+ * filled), for an ICMPv4 error message the embedded IPv4 header checksum first; SMOL_REC_IPHDR_ONLY and
+ * protocols emit does not checksum: payload verbatim; a record whose L4 check_len fails: payload
+ * verbatim, status SMOL_ST_MALFORMED, still cut.  In short, a cut datagram's frames are
+ * fragment_like_iface(emit(record), ip_mtu, ident, fill_header = caps.ipv4.tx()), each behind the
+ * record's Ethernet header if it has one.
+ *
+ * Cap and stride.  The datagram needs (count - 1) * S + last_len bytes.  When that exceeds cap, or when
+ * frame_stride != 0 && frame_stride < frame_len, nothing is stored and written = 0; count, frame_len
+ * and last_len are still reported, so the caller can size a retry.  Gaps between frames
+ * (frame_stride > frame length) are never written.
+ *
+ * Writes.  No byte of d_dst is ever read and none outside the frames of a written datagram is ever
+ * written; every byte of a frame is written exactly once.  Edges go out as byte-masked stores, never
+ * read-modify-write, so slots and frames may lie back to back at any alignment.  Slots must not overlap
+ * each other or the batch.
+ *
+ * Resources.  No context scratch, no event, no allocation; stream-ordered on `stream`, and calls on
+ * different streams are independent (also on one context).
+ *
+ * SMOL_EINVAL: NULL ctx, bad caps, NULL d_dst / d_plans / d_out with n > 0, d_plans or d_out not
+ * 16-byte aligned.  SMOL_ERANGE: as emit.  n == 0 returns SMOL_OK and launches nothing.
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive, as verify_reassemble was). */
+int smol_csum_batch_fragment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
+                                  const smol_checksum_caps_t* caps, uint8_t* d_dst,
+                                  const smol_csum_fragplan_t* d_plans, uint32_t frame_stride,
+                                  smol_csum_fragout_t* d_out, void* stream);
 
 /* ---- 4. 6LoWPAN next-header-compressed UDP (RFC 6282 §4.3) ------------------------------- */
 

@@ -186,7 +186,8 @@ const char* smol_csum_tool_kernel_name(const smol_csum_ctx_t* ctx, int op, int h
  * smol_csum_batch_emit_fields (variant 0): 7 = csum_kernel with the fields sink (the tools label it
  * "csum_fields_kernel"), 8 = xwalk_kernel with it, 9 = dwalk_kernel with it; 10 = vcopy_kernel
  * (smol_csum_batch_verify_copy); 11 = fragcopy_kernel (smol_csum_batch_verify_reassemble: variant 0,
- * G 64, U its chunks per lane and step); 0 before the first launch.  The fragment kernels of emit_frag /
+ * G 64, U its chunks per lane and step); 12 = fragcut_kernel (smol_csum_batch_fragment_emit: the same);
+ * 0 before the first launch.  The fragment kernels of emit_frag /
  * verify_frag record nothing. */
 uint32_t smol_csum_tool_last_launch(void);
 

@@ -33,7 +33,8 @@ ABI_SYMBOLS = [
     "smol_csum_batch_verify", "smol_csum_batch_copy_emit", "smol_csum_batch_emit_fields",
     "smol_csum_batch_verify_copy",
     "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
-    "smol_csum_batch_verify_frag", "smol_csum_batch_verify_reassemble", "smol_csum_batch_nhc_udp_emit",
+    "smol_csum_batch_verify_frag", "smol_csum_batch_verify_reassemble", "smol_csum_batch_fragment_emit",
+    "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
 ]
 TOOL_SYMBOLS = [
@@ -138,6 +139,30 @@ class DgramC(ctypes.Structure):
     ]
 
 
+class FragPlanC(ctypes.Structure):
+    """smol_csum_fragplan_t: where and how one datagram is cut (smol_csum_batch_fragment_emit)."""
+
+    _fields_ = [
+        ("dst_offset", ctypes.c_uint64),
+        ("cap", ctypes.c_uint32),
+        ("ip_mtu", ctypes.c_uint16),
+        ("ident", ctypes.c_uint16),
+    ]
+
+
+class FragOutC(ctypes.Structure):
+    """smol_csum_fragout_t: what became of one datagram (smol_csum_batch_fragment_emit)."""
+
+    _fields_ = [
+        ("count", ctypes.c_uint32),
+        ("frame_len", ctypes.c_uint32),
+        ("last_len", ctypes.c_uint32),
+        ("status", ctypes.c_uint8),
+        ("written", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint16),
+    ]
+
+
 _LIBS = {}
 
 
@@ -197,6 +222,9 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.smol_csum_batch_verify_reassemble.argtypes = [vp, vp, ctypes.POINTER(BatchC), vp, u64, ctypes.POINTER(Caps),
                                                         vp, vp, vp, vp, vp]
         L.smol_csum_batch_verify_reassemble.restype = i32
+    if hasattr(L, "smol_csum_batch_fragment_emit"):
+        L.smol_csum_batch_fragment_emit.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps), vp, vp, u32, vp, vp]
+        L.smol_csum_batch_fragment_emit.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []

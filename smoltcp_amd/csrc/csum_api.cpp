@@ -564,6 +564,37 @@ int smol_csum_batch_verify_reassemble(smol_csum_ctx_t* ctx, const uint8_t* d_buf
     return e == hipSuccess ? SMOL_OK : hip_fail(e, "verify_reassemble kernel launch");
 }
 
+// Emit with every whole IPv4 datagram cut into frames in its place of d_dst in the same pass
+// (include/smolcsum.h).  Uses none of the context's scratch or events, so calls on different streams are
+// independent.
+int smol_csum_batch_fragment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
+                                  const smol_checksum_caps_t* caps, uint8_t* d_dst, const smol_csum_fragplan_t* d_plans,
+                                  uint32_t frame_stride, smol_csum_fragout_t* d_out, void* stream) {
+    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
+    int rc = check_batch(b, d_buf);
+    if (rc != SMOL_OK || b->n == 0) return rc;
+    if (!d_dst || !d_plans || !d_out || ((uintptr_t)d_plans & 15u) != 0 || ((uintptr_t)d_out & 15u) != 0) return SMOL_EINVAL;
+    KParams p;
+    std::memset(&p, 0, sizeof p);
+    p.buf = const_cast<uint8_t*>(d_buf);  // (only read)
+    p.desc = b->desc;
+    p.n = b->n;
+    p.stride = b->stride;
+    p.len = b->len;
+    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
+    p.caps_ipv4 = caps->ipv4;
+    p.caps_udp = caps->udp;
+    p.caps_tcp = caps->tcp;
+    p.caps_icmpv4 = caps->icmpv4;
+    p.caps_icmpv6 = caps->icmpv6;
+    p.dummy = ctx->dummy;
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
+    const FragCutArgs v = {d_dst, d_plans, frame_stride, d_out};
+    const hipError_t e = launch_fragcut(p, v, (hipStream_t)stream);
+    return e == hipSuccess ? SMOL_OK : hip_fail(e, "fragment_emit kernel launch");
+}
+
 // ---- 6LoWPAN NHC UDP --------------------------------------------------------------------------
 
 int smol_csum_batch_nhc_udp_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,

@@ -1,0 +1,273 @@
+// Emit + fragmentation of whole IPv4 datagrams (smol_csum_batch_fragment_emit, include/smolcsum.h): the
+// mirror of csum_fragcopy.hip.  Each record is one datagram; its frames (Ethernet header if any, a fresh
+// IPv4 header, a slice of the payload) are written to the datagram's place in d_dst with every checksum
+// filled, in one pass over the payload.
+//
+// On transmit the reference reads a datagram it must fragment twice: it emits it whole into frag.buffer,
+// the L4 fill_checksum summing every byte (src/iface/interface/mod.rs:1263-1331), and then copies it out
+// a fragment at a time behind fresh headers (mod.rs:1334-1347, dispatch_ipv4_frag,
+// src/iface/interface/ipv4.rs:421-482).  Here every 16-B chunk of the payload is loaded once: the
+// registers are summed and the same registers feed the stores.
+//
+// One wavefront per datagram, four datagrams per 256-thread workgroup; no LDS, no barrier (the frames are
+// regular: frame k's payload is [k step, (k + 1) step), so there is no datagram map to share).
+//   1. Gate.  The wave parses the record with parse_geometry (csum_device.h, the emit flavour): the status
+//      byte, the L4 span and the offsets of the fields emit writes are emit's by construction.  The cut
+//      (count, frame lengths) and the cap / stride test follow; a datagram that is not cut or does not fit
+//      streams nothing.
+//   2. Streaming.  The wave walks the frames in order.  A frame's payload slice is streamed as 16-B chunks
+//      on the source's grid, U per lane and step, all loads of a step issued first, and the first step of
+//      the NEXT frame is issued before the current one is used.  Each chunk is summed as aligned words
+//      (edges masked, UDP capped at its length field: the tail is delivered, not summed) and funnelled
+//      onto the destination's 16-B grid exactly as fragcopy does (funnel16 of chunk slot k and its
+//      successor, taken from the next lane; lane 63's from one extra load).  The shift is per frame: the
+//      frame length is 2 or 4 mod 8.  Chunks entirely inside the slice go out as one dwordx4 store, a
+//      slice's first and last chunk byte-masked (store_edge).
+//   3. Frame head.  Lane i < io + 20 holds byte i of the record's headers; per frame it substitutes total
+//      length, ident, flags / offset and the header checksum (computed by every lane from the six words
+//      that do not change: a 10-word sum) and stores its byte.
+//   4. Held-back fields.  The L4 checksum bytes (payload offset 6, 16 or 2) and an ICMPv4 error's embedded
+//      header checksum (offset 18) are masked out of the streaming stores.  Once the last frame is summed
+//      the wave runs finish_gates (csum_walk.h, emit's own finish, its fields sink in a register) and lane 0
+//      writes each value to frame o / step at io + 20 + o % step: every byte of d_dst is written once, and
+//      nothing depends on the order of two stores.  step is a multiple of 8 and the offsets are even, so
+//      a field never straddles two frames.
+// No byte of d_dst is read.
+#include "csum_walk.h"
+
+namespace smolcsum {
+namespace fragcut {
+
+constexpr int U = 2;  // chunks per lane and step: a 1480-B slice is one step
+constexpr uint32_t STEP = 64 * U;
+constexpr int32_t NO_HOLD = -(1 << 30);
+
+__device__ __forceinline__ uint32_t rb(uint64_t a) { return *(gcu8)a; }
+__device__ __forceinline__ uint32_t rb16(uint64_t a) { return (rb(a) << 8) | rb(a + 1); }
+
+// One frame's payload slice (the same for every lane of the wave).
+struct Piece {
+    uint64_t base;     // chunk-grid origin: the slice's source address rounded down to 16
+    uint64_t D;        // destination address of the slice's first byte
+    uint64_t F;        // destination address of the frame's first byte
+    uint32_t head;     // source address - base
+    uint32_t nch;      // source chunks that hold a byte of the slice
+    uint32_t lead;     // 1: the chunk slots start one chunk before base (slot k holds chunk k - lead)
+    uint32_t nk;       // chunk slots: nch + lead
+    uint32_t sh;       // funnel shift: (head - dh) mod 16
+    uint32_t dh;       // D mod 16
+    uint32_t lo;       // datagram-payload offset of the slice
+    uint32_t sum_len;  // slice bytes summed (0: none)
+    uint32_t copy_len; // slice bytes delivered
+    int32_t h0, h1;    // slice-relative offsets of the held-back fields (far below 0: none)
+    uint32_t more;     // another frame follows (MF)
+};
+
+template <bool IMPLICIT>
+__global__ __launch_bounds__(256) void fragcut_kernel(KParams p, FragCutArgs v) {
+    using vcopy::next4;
+    using vcopy::store_edge;
+    using vcopy::sum_chunk;
+    const int lane = (int)(threadIdx.x & 63u);
+    const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint64_t dummy = (uint64_t)p.dummy;
+    const uint64_t nwaves = 4ull * gridDim.x;
+
+    for (uint64_t r = 4ull * blockIdx.x + wave; r < p.n; r += nwaves) {
+        // ---- 1. the gate: emit's parse, the cut, the cap ----
+        uint64_t a0;
+        uint32_t len, kind;
+        if (IMPLICIT) {
+            a0 = (uint64_t)p.buf + r * p.stride;
+            len = p.len;
+            kind = p.kind;
+        } else {
+            const u32x4 d = *(gcv4)((uint64_t)p.desc + 16 * r);
+            a0 = (uint64_t)p.buf + ((uint64_t)d.x | ((uint64_t)d.y << 32));
+            len = d.z;
+            kind = desc_kind(d.w);
+        }
+        auto rd = [&](uint32_t o) -> uint32_t { return rb(a0 + o); };
+        const Geom g = parse_geometry<false>(rd, len, kind, true);
+        const u32x4 pl = *(gcv4)((uint64_t)v.plans + 16ull * r);  // dst_offset, cap, ip_mtu | ident << 16
+        const uint32_t cap = pl.z, mtu = pl.w & 0xffffu, ident = pl.w >> 16;
+        const uint32_t io = g.ip_off, l4o = io + 20;
+        const uint64_t ip = a0 + io;
+        // cut: an IPv4 header that passed check_len (fam 4), IHL 5, not itself a fragment, ip_mtu >= 28
+        bool cut = g.fam == 4 && g.ip_hl == 20 && mtu >= 28;
+        uint32_t total = 20, id0 = 0, fl0 = 0;
+        if (cut) {
+            total = rb16(ip + 2);
+            id0 = rb16(ip + 4);
+            fl0 = rb16(ip + 6);
+            cut = (fl0 & 0x3fffu) == 0;
+        }
+        const uint32_t T = total - 20;
+        const uint32_t step = (mtu - 20) & ~7u;  // max_ipv4_fragment_size, phy/mod.rs:297-300
+        const bool single = 20 + T <= mtu;        // the iface sends it as it is, mod.rs:1276
+        uint32_t count = 0, frame_len = 0, last_len = 0;
+        if (cut) {
+            count = single ? 1u : (T + step - 1) / step;
+            frame_len = single ? l4o + T : l4o + step;
+            last_len = l4o + T - (count - 1) * (single ? 0u : step);
+        }
+        const uint32_t S = v.frame_stride ? v.frame_stride : frame_len;
+        const bool fits = cut && (uint64_t)(count - 1) * S + last_len <= cap && S >= frame_len;  // before the first store
+
+        if (fits) {
+            const bool l4 = g.proto != P_NONE && !(g.st & SMOL_ST_MALFORMED);
+            const uint32_t span = l4 ? g.span_end - l4o : 0u;  // payload bytes summed
+            const int32_t f1 = l4 ? (int32_t)g.fo : NO_HOLD;
+            const int32_t f2 = g.in_off ? (int32_t)(g.in_off - l4o + 10) : NO_HOLD;
+            const uint32_t pstep = single ? T : step;  // payload bytes of every frame but the last
+            const uint64_t Dbase = (uint64_t)v.dst + ((uint64_t)pl.x | ((uint64_t)pl.y << 32));
+            // the frame head: this lane's byte of the record's headers, and the header words no frame changes
+            const uint32_t hb = rb(a0 + ((uint32_t)lane < l4o ? (uint32_t)lane : 0u));
+            const uint32_t H0 = rb16(ip) + rb16(ip + 8) + rb16(ip + 12) + rb16(ip + 14) + rb16(ip + 16) + rb16(ip + 18);
+
+            auto setup = [&](uint32_t k) -> Piece {
+                Piece q;
+                q.lo = k * pstep;
+                const uint32_t hi = min(q.lo + pstep, T);
+                const uint64_t A = a0 + l4o + q.lo;
+                q.copy_len = hi - q.lo;
+                q.sum_len = span > q.lo ? min(span, hi) - q.lo : 0u;
+                q.base = A & ~15ull;
+                q.head = (uint32_t)(A - q.base);
+                q.nch = q.copy_len ? (uint32_t)(((A + q.copy_len + 15) >> 4) - (q.base >> 4)) : 0u;
+                q.F = Dbase + (uint64_t)k * S;
+                q.D = q.F + l4o;
+                q.dh = (uint32_t)(q.D & 15u);
+                q.sh = (q.head - q.dh) & 15u;
+                q.lead = q.copy_len && q.head < q.dh ? 1u : 0u;
+                q.nk = q.nch + q.lead;
+                q.h0 = f1 - (int32_t)q.lo;
+                q.h1 = f2 - (int32_t)q.lo;
+                q.more = k + 1 < count;
+                return q;
+            };
+            // one step: chunk slots [i0, i0 + STEP), and for lane 63 the slot after them
+            auto load = [&](const Piece& q, uint32_t i0, u32x4 (&c)[U], u32x4& xh) {
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const uint32_t k = i0 + (uint32_t)(u * 64 + lane) - q.lead;  // (slot 0 of a lead: wraps, >= nch)
+                    c[u] = ld16<false>((gcv4)(k < q.nch ? q.base + 16ull * k : dummy));
+                }
+                const uint32_t kx = i0 + STEP - q.lead;
+                xh = ld16<false>((gcv4)(lane == 63 && kx < q.nch ? q.base + 16ull * kx : dummy));
+            };
+            auto use = [&](const Piece& q, uint32_t i0, const u32x4 (&c)[U], const u32x4& xh, uint32_t& acc) {
+                if (q.sum_len) {
+#pragma unroll
+                    for (int u = 0; u < U; ++u) {
+                        const uint32_t k = i0 + (uint32_t)(u * 64 + lane) - q.lead;
+                        if (k < q.nch) acc = sum_chunk(c[u], (int)(16u * k) - (int)q.head, (int)q.sum_len, acc);
+                    }
+                }
+                // (the wave's lanes together: the exchange below needs all of them)
+                u32x4 ncur = next4<64>(c[0], lane);
+#pragma unroll
+                for (int u = 0; u < U; ++u) {
+                    const u32x4 nnext = u + 1 < U ? next4<64>(c[u + 1 < U ? u + 1 : u], lane) : xh;
+                    const u32x4 hi = lane == 63 ? nnext : ncur;
+                    ncur = nnext;
+                    const uint32_t k = i0 + (uint32_t)(u * 64 + lane);
+                    const int pos = (int)(16u * k) - (int)q.dh;  // slice-relative start of destination chunk k
+                    const int lo = -pos, end = (int)q.copy_len - pos;
+                    if (k < q.nk && end > 0 && lo < 16) {
+                        const u32x4 m = funnel16(c[u], hi, q.sh);
+                        const gu8 dst = (gu8)(q.D + (uint64_t)(int64_t)pos);
+                        const int a = max(lo, 0), b = min(end, 16);
+                        // a held-back field in this chunk (at most one: they lie 16 apart): the bytes around it
+                        int h = q.h0 - pos;
+                        if (!(h + 2 > a && h < b)) h = q.h1 - pos;
+                        if (h + 2 > a && h < b) {
+                            store_edge(dst, m, a, h);
+                            store_edge(dst, m, h + 2, b);
+                        } else if (lo <= 0 && end >= 16) {
+                            *(GMEM u32x4*)dst = m;
+                        } else {
+                            store_edge(dst, m, lo, end);
+                        }
+                    }
+                }
+            };
+            // the io + 20 header bytes of the frame, one byte per lane
+            auto head = [&](const Piece& q) {
+                const uint32_t tl = 20 + q.copy_len;
+                const uint32_t idk = single ? id0 : ident;
+                const uint32_t flk = single ? fl0 : ((q.more ? 0x2000u : 0u) | (q.lo >> 3));
+                const uint32_t cs = caps_tx(p.caps_ipv4) ? (~fold32(H0 + tl + idk + flk) & 0xffffu) : 0u;
+                const int j = lane - (int)io;
+                const uint32_t b = j == 2 ? tl >> 8 : j == 3 ? tl : j == 4 ? idk >> 8 : j == 5 ? idk
+                                 : j == 6 ? flk >> 8 : j == 7 ? flk : j == 10 ? cs >> 8 : j == 11 ? cs : hb;
+                if ((uint32_t)lane < l4o) ((gu8)q.F)[lane] = (uint8_t)b;
+            };
+
+            uint32_t acc = 0;  // this lane's part of the aligned-word sum over the summed payload bytes
+            {
+                Piece cur = setup(0u);
+                u32x4 c[U], xh;
+                load(cur, 0u, c, xh);
+                for (uint32_t k = 0; k < count; ++k) {
+                    Piece nxt = {};
+                    u32x4 cn[U], xn;
+                    if (k + 1 < count) {  // the next frame's first step, in flight under this one's work
+                        nxt = setup(k + 1);
+                        load(nxt, 0u, cn, xn);
+                    }
+                    head(cur);
+                    use(cur, 0u, c, xh, acc);
+                    for (uint32_t i0 = STEP; i0 < cur.nk; i0 += STEP) {
+                        load(cur, i0, c, xh);
+                        use(cur, i0, c, xh, acc);
+                    }
+                    cur = nxt;
+#pragma unroll
+                    for (int u = 0; u < U; ++u) c[u] = cn[u];
+                    xh = xn;
+                }
+            }
+
+            // ---- 4. emit's finish over the sums, and the held-back fields ----
+            if (l4) {
+                // finish_gates takes the lanes' sum over [0, span_end) and removes the header bytes [0, l4_off)
+                // itself: add them here, word for word as it removes them
+                const bool odd = (a0 & 1u) != 0;
+                for (uint32_t i = (uint32_t)lane; 2 * i < l4o; i += 64) {
+                    const uint32_t e = rd(2 * i), o = rd(2 * i + 1);
+                    acc += odd ? ((e << 8) + o) : (e + (o << 8));
+                }
+                // (its header window is the record itself here, head 0: the IPv4 header and address words are
+                // read from global memory, once per datagram)
+                u32x4 e = {0u, 0u, 0u, 0u};  // lane 0: smol_csum_fields_t (off[3], val[3], status)
+                finish_gates<64, MODE_EMIT, false, decltype(rd), 0, false, false, false, false, true, true>(
+                    p, g, acc, rd, (const uint8_t*)a0, 0u, a0, r, lane, nullptr, ~0ull, ~0ull, 0, &e);
+                if (lane == 0) {
+                    auto put = [&](int32_t f, uint32_t val) {
+                        const uint32_t k = (uint32_t)f / pstep, o = (uint32_t)f % pstep;
+                        store_be16((gu8)(Dbase + (uint64_t)k * S + l4o + o), val);
+                    };
+                    put(f1, e.z & 0xffffu);
+                    if (f2 != NO_HOLD) put(f2, e.z >> 16);
+                }
+            }
+        }
+        if (lane == 0) {  // smol_csum_fragout_t: count, frame_len, last_len, status | written << 8
+            const u32x4 o = {count, frame_len, last_len, (g.st & 0xffu) | (fits ? 0x100u : 0u)};
+            *(GMEM u32x4*)((uint64_t)v.out + 16ull * r) = o;
+        }
+    }
+}
+
+}  // namespace fragcut
+
+hipError_t launch_fragcut(const KParams& p, const FragCutArgs& v, hipStream_t s) {
+    const uint32_t blocks = grid_blocks((p.n + 3) / 4, kMaxGridBlocks);
+    note_launch(KERN_FRAGCUT, 0, 64, fragcut::U);
+    if (p.desc == nullptr) hipLaunchKernelGGL((fragcut::fragcut_kernel<true>), dim3(blocks), dim3(256), 0, s, p, v);
+    else hipLaunchKernelGGL((fragcut::fragcut_kernel<false>), dim3(blocks), dim3(256), 0, s, p, v);
+    return hipGetLastError();
+}
+
+}  // namespace smolcsum

@@ -497,12 +497,15 @@ __device__ __forceinline__ void stage_record(const KParams& p, uint64_t r, bool 
 // p.fields + r with one non-temporal 16-B store; nothing goes into the record and no status byte is
 // written.  The finishing lanes of a wavefront hold consecutive records, so their entries leave as one
 // contiguous run (8 records per wavefront: one 128-B line per store instruction).
+// FREG (with FLD; csum_fragcut.hip): lane 0's entry goes to *freg, a register of the caller's, instead of
+// p.fields: the caller writes the values where its own layout wants them.
 template <int G, int MODE, bool NHC, class RD, int WINB = 0, bool SEGP = false, bool NOSTORE = false,
-          bool NTST = false, bool STG = false, bool FLD = false>
+          bool NTST = false, bool STG = false, bool FLD = false, bool FREG = false>
 __device__ __forceinline__ void finish_gates(const KParams& p, const Geom& g, uint32_t acc, const RD& rd,
                                              const uint8_t* winb, uint32_t head, uint64_t a0, uint64_t r,
                                              int lane, uint8_t* winw = nullptr, uint64_t wsA = ~0ull,
-                                             uint64_t wsB = ~0ull, int stg = 0) {
+                                             uint64_t wsB = ~0ull, int stg = 0, u32x4* freg = nullptr) {
+    static_assert(!FREG || FLD, "FREG: the fields sink in a register");
     constexpr bool EMITS = MODE == MODE_EMIT || MODE == MODE_COPY;
     const bool odd = (a0 & 1u) != 0;
     // Header bytes [0, l4_off) that the lanes summed (taken out of the L4 sum), the IPv4
@@ -646,7 +649,8 @@ __device__ __forceinline__ void finish_gates(const KParams& p, const Geom& g, ui
             e.y = off(fin) | (vip & 0xffffu) << 16;
             e.z = (vl4 & 0xffffu) | (vin & 0xffffu) << 16;
             e.w = st & 0xffu;
-            __builtin_nontemporal_store(e, (GMEM u32x4*)((uint64_t)p.fields + 16ull * r));
+            if constexpr (FREG) *freg = e;
+            else __builtin_nontemporal_store(e, (GMEM u32x4*)((uint64_t)p.fields + 16ull * r));
         } else if (EMITS && SEGP) {
             auto put = [&](uint32_t f, uint32_t v) {
                 const uint64_t x0 = (a0 + f) & ~63ull, x1 = (a0 + f + 1) & ~63ull;

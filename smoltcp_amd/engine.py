@@ -16,7 +16,7 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import NO_FIELD, BatchC, Caps, DgramC, FieldsC, SlotC, SpanC, check, lib
+from ._lib import NO_FIELD, BatchC, Caps, DgramC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, check, lib
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -63,6 +63,12 @@ assert SPAN_DTYPE.itemsize == 8 == ctypes.sizeof(SpanC)
 DGRAM_DTYPE = np.dtype([("len", "<u4"), ("l4_len", "<u4"), ("l4_off", "<u2"), ("protocol", "u1"), ("copied", "u1"),
                         ("reserved", "<u4")])
 assert DGRAM_DTYPE.itemsize == 16 == ctypes.sizeof(DgramC)
+# smol_csum_fragplan_t / smol_csum_fragout_t: one datagram's cut and what became of it (smol_csum_batch_fragment_emit)
+FRAGPLAN_DTYPE = np.dtype([("dst_offset", "<u8"), ("cap", "<u4"), ("ip_mtu", "<u2"), ("ident", "<u2")])
+assert FRAGPLAN_DTYPE.itemsize == 16 == ctypes.sizeof(FragPlanC)
+FRAGOUT_DTYPE = np.dtype([("count", "<u4"), ("frame_len", "<u4"), ("last_len", "<u4"), ("status", "u1"), ("written", "u1"),
+                          ("reserved", "<u2")])
+assert FRAGOUT_DTYPE.itemsize == 16 == ctypes.sizeof(FragOutC)
 
 
 def make_slots(dst_offsets, caps) -> np.ndarray:
@@ -72,6 +78,17 @@ def make_slots(dst_offsets, caps) -> np.ndarray:
     s["dst_offset"] = np.asarray(dst_offsets, dtype=np.uint64)
     s["cap"] = np.broadcast_to(np.asarray(caps, dtype=np.uint32), (n,))
     return s
+
+
+def make_fragplans(dst_offsets, caps, ip_mtus, idents) -> np.ndarray:
+    """Host array of smol_csum_fragplan_t (view it as uint8 and copy it to the device)."""
+    n = len(dst_offsets)
+    p = np.zeros(n, dtype=FRAGPLAN_DTYPE)
+    p["dst_offset"] = np.asarray(dst_offsets, dtype=np.uint64)
+    p["cap"] = np.broadcast_to(np.asarray(caps, dtype=np.uint32), (n,))
+    p["ip_mtu"] = np.broadcast_to(np.asarray(ip_mtus, dtype=np.uint16), (n,))
+    p["ident"] = np.broadcast_to(np.asarray(idents, dtype=np.uint16), (n,))
+    return p
 
 
 def apply_fields(host_buf: np.ndarray, record_offsets, record_lens, fields) -> np.ndarray:
@@ -338,6 +355,30 @@ class ChecksumEngine:
               "smol_csum_batch_verify_reassemble")
         return status, dgrams
 
+    def fragment_emit(self, buf, batch: Batch, dst, plans, frame_stride: int = 0, caps=None, out=None, stream=None):
+        """Emit, and in the same pass every whole IPv4 datagram of the batch cut into the frames the iface
+        sends, at its place in `dst` (smol_csum_batch_fragment_emit).  `plans`: a device uint8 tensor of one
+        smol_csum_fragplan_t per record (see make_fragplans); `frame_stride`: bytes from one frame of a
+        datagram to the next (0: back to back); `dst`: the destination uint8 device tensor, written only
+        inside the frames.  Returns an n x 16 uint8 device tensor of smol_csum_fragout_t (view its host copy
+        as FRAGOUT_DTYPE).  `buf` is only read."""
+        import torch
+
+        self._check_buf(buf, batch)
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert plans.is_cuda and plans.is_contiguous() and plans.numel() * plans.dtype.itemsize >= 16 * batch.n
+        assert 0 <= int(frame_stride) < 1 << 32
+        if out is None:
+            out = torch.empty((batch.n, 16), dtype=torch.uint8, device=buf.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.dtype.itemsize >= 16 * batch.n
+        b = batch.c()
+        c = _caps(caps)
+        check(self._L.smol_csum_batch_fragment_emit(self._h, buf.data_ptr(), ctypes.byref(b), ctypes.byref(c),
+                                                  dst.data_ptr(), plans.data_ptr(), int(frame_stride),
+                                                  out.data_ptr(), self._stream(stream)),
+              "smol_csum_batch_fragment_emit")
+        return out
+
     def nhc_udp_emit(self, buf, batch: Batch, addrs, caps=None, status=None, stream=None):
         """6LoWPAN NHC UDP emit (smol_csum_batch_nhc_udp_emit): ``addrs`` is a device uint8 tensor of
         n x 32 bytes (IPv6 source, destination per record)."""
@@ -501,13 +542,13 @@ class ChecksumEngine:
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
         "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
-        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel", "variant": VAR, "G":
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
                  6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel",
-                 11: "fragcopy_kernel"}
+                 11: "fragcopy_kernel", 12: "fragcut_kernel"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

@@ -267,6 +267,19 @@ public:
                                                 d_dgrams, stream),
               "smol_csum_batch_verify_reassemble");
     }
+    // emit, and in the same pass every whole IPv4 datagram cut into the frames the iface sends (dispatch_ip's
+    // first fragment, src/iface/interface/mod.rs:1276-1347, and dispatch_ipv4_frag's others, ipv4.rs:421-482),
+    // at d_plans[i].dst_offset of d_dst, frame k at + k * frame_stride (0: back to back); d_out[i] = the frame
+    // count and lengths, emit's status byte and whether the frames were stored.  d_plans / d_out: one per
+    // record.  d_buf is only read.
+    void fragment_emit(const uint8_t* d_buf, const Batch& b, uint8_t* d_dst, const smol_csum_fragplan_t* d_plans,
+                       smol_csum_fragout_t* d_out, uint32_t frame_stride = 0,
+                       const smoltcp::phy::ChecksumCapabilities& caps = {}, void* stream = nullptr) {
+        auto bc = b.c();
+        auto cc = caps.c();
+        check(smol_csum_batch_fragment_emit(ctx_, d_buf, &bc, &cc, d_dst, d_plans, frame_stride, d_out, stream),
+              "smol_csum_batch_fragment_emit");
+    }
 
     // 6LoWPAN NHC UDP (sixlowpan::nhc::UdpNhcRepr::emit / ::parse): every record is a LOWPAN_NHC
     // UDP packet; d_addrs[i] holds record i's IPv6 addresses (IPHC-decompressed).

@@ -1,0 +1,321 @@
+"""GPU parity of fragment_emit (smol_csum_batch_fragment_emit): whole IPv4 datagrams cut into the frames the
+iface sends, every checksum filled, in one pass.
+
+Every case compares, exactly:
+  1. the smol_csum_fragout_t entries with tests/fragment_ref.py (oracle.batch_emit's status byte included);
+  2. the WHOLE destination arena, filled with the sentinel 0xA5 beforehand, with the helper's: a stray store
+     or a missing byte anywhere fails;
+  3. the batch buffer with what was uploaded: it is only read;
+and checks that the launch recorded is fragcut_kernel.
+"""
+import numpy as np
+import pytest
+
+from tests import fragment_ref as C
+from tests import pktgen as P
+from tests import test_frag_cpu as F
+
+torch = pytest.importorskip("torch")
+pytestmark = pytest.mark.gpu
+
+from smoltcp_amd import engine as E  # noqa: E402
+
+NOCAPS = (0, 0, 0, 0, 0)
+GARBAGE = 0xBEEF  # what the checksum fields hold before the call: never summed, always overwritten
+MTUS = (28, 68, 576, 1280, 1500)
+PROTOS = ("udp", "tcp", "echo", "error", "igmp", "gre")
+
+
+@pytest.fixture(scope="module")
+def eng():
+    assert torch.cuda.is_available(), "GPU tests need a HIP device"
+    e = E.ChecksumEngine(0)
+    yield e
+    e.close()
+
+
+def _dgram(rng, proto: str, T: int, ident: int = 0x7777, flags_frag: int = 0x4000) -> bytes:
+    """An IPv4 datagram (IHL 5, DF set, checksum fields holding garbage) with exactly T payload bytes of
+    the given protocol; a T too small for the protocol's header gives a truncated one (check_len fails)."""
+    def fit(b: bytes) -> bytes:
+        return (b + P.rand_bytes(rng, max(T - len(b), 0)))[:T]
+
+    if proto == "udp":
+        num, l4 = 17, P.udp(4000, 53, P.rand_bytes(rng, T - 8), csum=GARBAGE) if T >= 8 else fit(b"")
+    elif proto == "tcp":
+        num, l4 = 6, P.tcp(4001, 80, P.rand_bytes(rng, T - 20), csum=GARBAGE) if T >= 20 else fit(b"")
+    elif proto == "echo":
+        num, l4 = 1, P.icmp_echo(8, P.rand_bytes(rng, T - 8), csum=GARBAGE) if T >= 8 else fit(b"\x08")
+    elif proto == "error":  # DstUnreachable carrying an IPv4 header (its checksum field garbage too) when it fits
+        num = 1
+        inner = P.ipv4(F.B, F.A, 17, P.rand_bytes(rng, max(T - 28, 0)), csum=GARBAGE)
+        l4 = P.icmp4_error(3, 3, inner, csum=GARBAGE) if T >= 28 else fit(b"\x03\x03" + P.be16(GARBAGE))
+    elif proto == "igmp":
+        num, l4 = 2, fit(b"\x11\x0a" + P.be16(GARBAGE) + bytes([224, 0, 0, 1]))
+    else:
+        num, l4 = 47, fit(b"")
+    assert len(l4) == T
+    return P.ipv4(F.A, F.B, num, l4, flags_frag=flags_frag, ident=ident, csum=GARBAGE)
+
+
+def _run(eng, recs, kind=E.KIND_IP, flags=0, mtu=576, idents=None, stride=0, caps=NOCAPS, fixed=None, start=3,
+         cap_adj=0, seed=0):
+    """One fragment_emit call, compared exactly.  recs: the records; kind / flags / mtu / idents / cap_adj:
+    one for all or one per record; fixed: (record stride, base offset) for a fixed-stride batch, else a
+    descriptor batch with random gaps (odd offsets).  Slots lie back to back from `start`, each as large as
+    its datagram needs; cap = that + cap_adj.  Returns (out entries, arena, slot offsets)."""
+    n = len(recs)
+    kinds = np.broadcast_to(np.asarray(kind, np.uint8), (n,)).copy()
+    flags_a = np.broadcast_to(np.asarray(flags, np.uint8), (n,)).copy()
+    mtus = np.broadcast_to(np.asarray(mtu, np.uint16), (n,)).copy()
+    idents = 0x4000 + np.arange(n) if idents is None else idents
+    if fixed is not None:
+        rstride, base = fixed
+        buf = np.random.default_rng(seed).integers(0, 256, base + n * rstride + 64, dtype=np.uint8)
+        offs = base + np.arange(n, dtype=np.uint64) * rstride
+        for o, r in zip(offs, recs):
+            assert len(r) <= rstride
+            buf[int(o):int(o) + len(r)] = np.frombuffer(r, np.uint8)
+        lens = np.full(n, rstride, np.uint32)
+        assert (kinds == kinds[0]).all() and (flags_a == flags_a[0]).all()
+    else:
+        buf, offs, lens = P.pack(recs, gap_rng=np.random.default_rng(seed))
+    placed = [bytes(buf[int(o):int(o) + int(ln)]) for o, ln in zip(offs, lens)]
+    # a first pass of the helper with caps of 0 reports what every datagram needs
+    size = C.expected(placed, kinds, flags_a, E.make_fragplans(np.zeros(n), 0, mtus, idents), stride, caps, 1)[0]
+    need = np.where(size["count"] > 0, (size["count"].astype(np.int64) - 1) *
+                    np.where(stride, stride, size["frame_len"]).astype(np.int64) + size["last_len"], 0)
+    slot = np.concatenate([[start], start + np.cumsum(need)]).astype(np.int64)
+    arena_size = int(slot[-1]) + 21
+    plans = E.make_fragplans(slot[:-1], np.maximum(need + cap_adj, 0), mtus, idents)
+    ref_out, ref_arena = C.expected(placed, kinds, flags_a, plans, stride, caps, arena_size)
+
+    if fixed is not None:
+        batch = E.Batch.fixed(n, fixed[0], fixed[0], int(kinds[0]), flags=int(flags_a[0]))
+    else:
+        batch = E.Batch.from_records(offs, lens, kinds, "cuda:0", flags=flags_a)
+    d = torch.from_numpy(buf.copy()).cuda()
+    dv = d[fixed[1]:] if fixed is not None else d
+    dst = torch.full((arena_size,), C.SENTINEL, dtype=torch.uint8, device="cuda")
+    pd = torch.from_numpy(plans.view(np.uint8).copy()).cuda()
+    out = eng.fragment_emit(dv, batch, dst, pd, frame_stride=stride, caps=caps)
+    launched = eng.last_launch()
+    got_out = out.cpu().numpy().reshape(-1).view(E.FRAGOUT_DTYPE)
+    got_dst = dst.cpu().numpy()
+    assert launched["kernel"] == "fragcut_kernel", launched
+    assert np.array_equal(d.cpu().numpy(), buf), "the batch buffer is only read"
+    bad = np.nonzero(got_out != ref_out)[0]
+    assert bad.size == 0, f"entries differ at {bad[:8]}: got {got_out[bad[:4]]} want {ref_out[bad[:4]]}"
+    diff = np.nonzero(got_dst != ref_arena)[0]
+    assert diff.size == 0, f"destination bytes differ at {diff[:8]} (got {got_dst[diff[:8]]} want {ref_arena[diff[:8]]})"
+    return got_out, got_dst, slot[:-1]
+
+
+# ---- 1. the size sweep ---------------------------------------------------------------------------
+
+def _sweep_sizes(mtu):
+    step = (mtu - 20) - (mtu - 20) % 8
+    return [0] + [step * k + d for k in (1, 2, 5) for d in (-8, -1, 0, 1, 8)]
+
+
+@pytest.mark.parametrize("layout", ["desc-0", "desc-1500", "desc-odd", "fixed-0", "fixed-1500", "fixed-odd"])
+@pytest.mark.parametrize("eth", [False, True])
+@pytest.mark.parametrize("mtu", MTUS)
+def test_size_sweep(eng, mtu, eth, layout):
+    """Every protocol at every payload length around 1, 2 and 5 steps, and 0; frames back to back
+    (frame_stride 0), at 1500 + io (above every frame length here) and at an odd stride."""
+    form, s = layout.split("-")
+    io = 14 if eth else 0
+    stride = {"0": 0, "1500": 1500 + io, "odd": 1521 + io}[s]
+    rng = np.random.default_rng(mtu * 4 + eth * 2 + (form == "fixed"))
+    recs = [_dgram(rng, p, T) for T in _sweep_sizes(mtu) for p in PROTOS]
+    if eth:
+        recs = [P.eth(r) for r in recs]
+    fixed = (max(len(r) for r in recs) + 3, 5) if form == "fixed" else None
+    out, _, _ = _run(eng, recs, kind=E.KIND_ETH if eth else E.KIND_IP, mtu=mtu, stride=stride, fixed=fixed, seed=mtu)
+    assert (out["written"] == 1).all()
+    if mtu == 28:  # the held-back fields land in frame 2: TCP's at 16, the ICMPv4 error's embedded one at 18
+        assert (out["count"].reshape(-1, len(PROTOS))[-5:] >= 4).all()
+
+
+@pytest.mark.parametrize("form", ["desc", "fixed"])
+@pytest.mark.parametrize("eth", [False, True])
+@pytest.mark.parametrize("mtu", MTUS)
+def test_largest_datagram(eng, mtu, eth, form):
+    """T = 65515 (total length 65535), TCP and an ICMPv4 error, among smaller neighbours."""
+    rng = np.random.default_rng(mtu + 100 * eth)
+    recs = [_dgram(rng, "udp", 700), _dgram(rng, "tcp", 65515), _dgram(rng, "echo", 99), _dgram(rng, "error", 65515),
+            _dgram(rng, "udp", 65515)]
+    if eth:
+        recs = [P.eth(r) for r in recs]
+    fixed = (max(len(r) for r in recs) + 1, 9) if form == "fixed" else None
+    out, _, _ = _run(eng, recs, kind=E.KIND_ETH if eth else E.KIND_IP, mtu=mtu, fixed=fixed, seed=mtu)
+    step = (mtu - 20) - (mtu - 20) % 8
+    assert int(out[1]["count"]) == -(-65515 // step) and (out["written"] == 1).all()
+
+
+def test_every_destination_alignment(eng):
+    """Slots back to back whose lengths are 1 mod 16: the slot offsets take every value mod 16, and with an
+    odd frame length so do the frames; sources at random odd offsets."""
+    rng = np.random.default_rng(5)
+    recs = []
+    for i in range(48):
+        mtu, step = 68, 48
+        T = 100 + i
+        while ((-(-T // step)) * 20 + T) % 16 != 1:  # count * 20 + T: what the datagram needs
+            T += 1
+        recs.append(_dgram(rng, PROTOS[i % 4], T))
+    out, _, slots = _run(eng, recs, mtu=68, start=0)
+    assert {int(s) % 16 for s in slots} == set(range(16))
+    _run(eng, recs, mtu=68, start=0, stride=69)
+
+
+# ---- 2. values -----------------------------------------------------------------------------------
+
+def test_udp_checksum_zero_becomes_ffff(eng):
+    rng = np.random.default_rng(8)
+    recs = []
+    for T in (1200, 64):
+        d = bytearray(_dgram(rng, "udp", T))
+        # the checksum c = !sum as the oracle computes it; raising one payload word by c (mod 0xffff) makes
+        # the sum 0xffff and the computed checksum 0
+        c = int.from_bytes(C.emit_record(bytes(d), E.KIND_IP, 0, NOCAPS)[1][26:28], "big")
+        w = int.from_bytes(d[30:32], "big")
+        d[30:32] = ((w + c) % 0xFFFF).to_bytes(2, "big")
+        assert C.emit_record(bytes(d), E.KIND_IP, 0, NOCAPS)[1][26:28] == b"\xff\xff"
+        recs.append(bytes(d))
+    _, arena, slots = _run(eng, recs, mtu=576)
+    assert arena[int(slots[0]) + 26:int(slots[0]) + 28].tobytes() == b"\xff\xff"
+    assert arena[int(slots[1]) + 26:int(slots[1]) + 28].tobytes() == b"\xff\xff"
+
+
+def test_udp_length_below_payload_tail_delivered_not_summed(eng):
+    rng = np.random.default_rng(9)
+    recs = []
+    for T, ul in ((1400, 1001), (1400, 8), (3000, 2048), (200, 199), (700, 552), (700, 553)):
+        recs.append(P.ipv4(F.A, F.B, 17, P.udp(7, 9, P.rand_bytes(rng, T - 8), csum=GARBAGE, length=ul)))
+    recs.append(P.ipv4(F.A, F.B, 17, P.udp(7, 9, P.rand_bytes(rng, 92), csum=GARBAGE, length=101)))  # above T: MALFORMED, still cut
+    out, _, _ = _run(eng, recs, mtu=576)
+    assert out["status"].tolist() == [0] * 6 + [E.ST_MALFORMED] and (out["written"] == 1).all()
+    _run(eng, [P.eth(r) for r in recs], kind=E.KIND_ETH, mtu=68)
+
+
+@pytest.mark.parametrize("ipv4_caps", [0, 1, 2, 3])
+def test_every_caps_combination(eng, ipv4_caps):
+    """caps.ipv4 x the record's own L4 caps in {Both, Rx, Tx, None}; IGMP is filled whatever the caps."""
+    rng = np.random.default_rng(10 + ipv4_caps)
+    recs = [_dgram(rng, p, T) for p in PROTOS for T in (1300, 40)]
+    for l4 in range(4):
+        _run(eng, recs, mtu=576, caps=(ipv4_caps, l4, l4, l4, 0), seed=l4)
+    _run(eng, recs, mtu=576, caps=(ipv4_caps, 0, 1, 2, 3))
+
+
+def test_iphdr_only_payload_verbatim(eng):
+    rng = np.random.default_rng(11)
+    recs = [_dgram(rng, p, T) for p in PROTOS for T in (1300, 40)]
+    out, _, _ = _run(eng, recs, mtu=576, flags=E.REC_IPHDR_ONLY)
+    assert (out["status"] == E.ST_UNSUPPORTED).all() and (out["written"] == 1).all()
+    fixed = (max(len(r) for r in recs), 0)
+    _run(eng, recs, mtu=576, flags=E.REC_IPHDR_ONLY, fixed=fixed)
+    mixed = np.arange(len(recs)) % 2 * E.REC_IPHDR_ONLY
+    _run(eng, recs, mtu=68, flags=mixed)
+
+
+# ---- 3. records that are not cut -----------------------------------------------------------------
+
+def test_records_not_cut_neighbours_served(eng):
+    rng = np.random.default_rng(12)
+    good = lambda: _dgram(rng, "udp", 1000)  # noqa: E731
+    v6 = P.ipv6(bytes(range(16)), bytes(range(16, 32)), 17, P.udp(7, 9, P.rand_bytes(rng, 600)))
+    u = P.udp(7, 9, P.rand_bytes(rng, 600))
+    not_cut = [
+        (v6, E.KIND_IP),
+        (P.eth(v6, 0x86DD), E.KIND_ETH),
+        (P.eth(good(), 0x0806), E.KIND_ETH),
+        (good(), E.KIND_RAW),
+        (P.ipv4(F.A, F.B, 17, u, ihl=6), E.KIND_IP),
+        (P.ipv4(F.A, F.B, 17, u, flags_frag=0x2000), E.KIND_IP),  # MF set
+        (P.ipv4(F.A, F.B, 17, u, flags_frag=0x0010), E.KIND_IP),  # offset set
+        (P.ipv4(F.A, F.B, 17, u, flags_frag=0x2040), E.KIND_IP),
+        (P.ipv4(F.A, F.B, 17, u, total_len=700), E.KIND_IP),      # check_len: total above the record
+        (P.ipv4(F.A, F.B, 17, u, total_len=19), E.KIND_IP),       # check_len: total below the header
+        (good()[:19], E.KIND_IP),
+        (P.eth(good())[:13], E.KIND_ETH),
+        (bytes([0x55]) + good()[1:], E.KIND_IP),                  # version 5
+    ]
+    recs, kinds = [], []
+    for r, k in not_cut:
+        recs += [good(), r, P.eth(good())]
+        kinds += [E.KIND_IP, k, E.KIND_ETH]
+    out, _, _ = _run(eng, recs, kind=kinds, mtu=576, cap_adj=np.where(np.arange(len(recs)) % 3 == 1, 4000, 0))
+    assert (out["count"][1::3] == 0).all() and (out["written"][1::3] == 0).all()
+    assert (out["count"][0::3] == 2).all() and (out["written"][0::3] == 1).all() and (out["written"][2::3] == 1).all()
+    # ip_mtu 27 on some records of a batch, 28 on the others
+    recs = [_dgram(rng, PROTOS[i % 6], 40 + i) for i in range(24)]
+    mtus = np.where(np.arange(24) % 3 == 0, 27, 28)
+    out, _, _ = _run(eng, recs, mtu=mtus)
+    assert (out["count"][0::3] == 0).all() and (out["count"][1::3] > 0).all() and (out["written"][0::3] == 0).all()
+
+
+# ---- 4. cap and stride ---------------------------------------------------------------------------
+
+def test_cap_one_byte_short_and_stride_below_frame_len(eng):
+    rng = np.random.default_rng(13)
+    recs = [_dgram(rng, PROTOS[i % 6], T) for i, T in enumerate((1000, 3000, 552, 553, 100, 0, 5000, 556, 1104, 1105, 2000, 548))]
+    short = np.where(np.arange(len(recs)) % 2 == 0, -1, 0)
+    out, arena, slots = _run(eng, recs, mtu=576, cap_adj=short)
+    assert out["written"].tolist() == [0, 1] * 6 and (out["count"] > 0).all()
+    out, arena, _ = _run(eng, recs, mtu=576, cap_adj=-1)
+    assert (out["written"] == 0).all() and (arena == C.SENTINEL).all() and (out["frame_len"] > 0).all()
+    # frame_len is 572 for the fragmented ones: a stride of 571 stores none of them, the single frames of
+    # at most 571 bytes still go out
+    out, arena, _ = _run(eng, recs, mtu=576, stride=571, cap_adj=10000)
+    assert out["written"].tolist() == [int(fl) <= 571 for fl in out["frame_len"]]
+    assert out["written"].sum() == 3
+    out, _, _ = _run(eng, [P.eth(r) for r in recs], kind=E.KIND_ETH, mtu=576, stride=585, cap_adj=short)
+    assert out["written"].tolist() == [int(fl) <= 585 and i % 2 == 1 for i, fl in enumerate(out["frame_len"])]
+
+
+# ---- 5. round trip -------------------------------------------------------------------------------
+
+@pytest.mark.parametrize("mtu,eth", [(68, True), (576, False), (1500, True)])
+def test_round_trip_through_verify_reassemble(eng, mtu, eth):
+    """frame_stride = io + ip_mtu: d_dst is a fixed-stride batch of frames; verify_reassemble accepts every
+    record and returns each datagram's emitted payload."""
+    rng = np.random.default_rng(mtu + 7)
+    io = 14 if eth else 0
+    kind = E.KIND_ETH if eth else E.KIND_IP
+    small = mtu == 68
+    dgs = F.datagrams(rng, 24, 20 if small else 200, 700 if small else 6000)
+    recs = [P.eth(x) for x in dgs] if eth else dgs
+    S = io + mtu
+    buf, offs, lens = P.pack(recs, gap_rng=rng)
+    batch = E.Batch.from_records(offs, lens, kind, "cuda:0")
+    T = [len(x) - 20 for x in dgs]
+    step = (mtu - 20) - (mtu - 20) % 8
+    counts = [1 if 20 + t <= mtu else -(-t // step) for t in T]
+    firsts = np.concatenate([[0], np.cumsum(counts)[:-1]])
+    nrec = int(sum(counts))
+    plans = E.make_fragplans(firsts * S, np.array(counts) * S, mtu, 0x100 + np.arange(len(dgs)))
+    dst = torch.zeros(nrec * S, dtype=torch.uint8, device="cuda")
+    out = eng.fragment_emit(torch.from_numpy(buf).cuda(), batch, dst, torch.from_numpy(plans.view(np.uint8).copy()).cuda(),
+                            frame_stride=S)
+    out = out.cpu().numpy().reshape(-1).view(E.FRAGOUT_DTYPE)
+    assert out["count"].tolist() == counts and (out["written"] == 1).all() and (out["status"] == 0).all()
+    frames = E.Batch.fixed(nrec, S, S, kind)
+    gd = torch.from_numpy(E.make_groups(firsts, counts).view(np.uint8).copy()).cuda()
+    so = np.concatenate([[0], np.cumsum(T)[:-1]])
+    back = torch.full((sum(T) + 1,), 0xA5, dtype=torch.uint8, device="cuda")
+    st, dg = eng.verify_reassemble(dst, frames, gd, back, torch.from_numpy(E.make_slots(so, T).view(np.uint8).copy()).cuda())
+    assert bool((st & E.ST_ACCEPT).all())
+    dg = dg.cpu().numpy().reshape(-1).view(E.DGRAM_DTYPE)
+    assert dg["len"].tolist() == T and (dg["copied"] == 1).all()
+    want = b"".join(F.emit_whole(x, F.DEFAULT)[20:] for x in dgs) + b"\xa5"
+    assert back.cpu().numpy().tobytes() == want
+
+
+def test_many_datagrams_grid_stride(eng):
+    """More datagrams than one workgroup holds, count not a multiple of 4."""
+    rng = np.random.default_rng(14)
+    recs = [_dgram(rng, PROTOS[i % 6], 30 + (i * 37) % 900) for i in range(203)]
+    _run(eng, recs, mtu=np.where(np.arange(203) % 2, 68, 576))
