@@ -117,6 +117,75 @@ int check_batch(const smol_csum_batch_t* b, const void* d_buf) {
     return SMOL_OK;
 }
 
+// What a batched call with caps checks first, in this order: the context and the caps, then the batch.
+// False: the call ends here with *rc (an error, or SMOL_OK for an empty batch).
+bool begin_call(const smol_csum_ctx_t* ctx, const smol_checksum_caps_t* caps, const smol_csum_batch_t* b,
+                const void* d_buf, int* rc) {
+    *rc = !ctx || !caps_valid(caps) ? SMOL_EINVAL : check_batch(b, d_buf);
+    return *rc == SMOL_OK && b->n != 0;
+}
+
+// The same for a call over fragment groups: no groups is SMOL_OK whatever the batch holds, groups over an
+// empty batch are an error.
+bool begin_group_call(const smol_csum_ctx_t* ctx, const smol_checksum_caps_t* caps, const smol_csum_batch_t* b,
+                      const void* d_buf, const smol_csum_frag_group_t* d_groups, uint64_t n_groups, int* rc) {
+    *rc = !ctx || !caps_valid(caps) ? SMOL_EINVAL : check_batch(b, d_buf);
+    if (*rc != SMOL_OK || n_groups == 0) return false;
+    if (b->n == 0 || !d_groups || ((uintptr_t)d_groups & 15u) != 0) *rc = SMOL_EINVAL;
+    return *rc == SMOL_OK;
+}
+
+uint32_t cu_count(const smol_csum_ctx_t* ctx) { return (uint32_t)(ctx->num_cu > 0 ? ctx->num_cu : 256); }
+
+// Zeroed launch parameters with what every batched call takes from its arguments: the batch form, the
+// record kind, the caps (none: smol_csum_batch_data) and the dummy line.
+KParams base_params(const smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
+                    const smol_checksum_caps_t* caps) {
+    KParams p;
+    std::memset(&p, 0, sizeof p);
+    p.buf = const_cast<uint8_t*>(d_buf);  // (only emit and copy_emit store there)
+    p.desc = b->desc;
+    p.n = b->n;
+    p.stride = b->stride;
+    p.len = b->len;
+    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
+    if (caps) {
+        p.caps_ipv4 = caps->ipv4;
+        p.caps_udp = caps->udp;
+        p.caps_tcp = caps->tcp;
+        p.caps_icmpv4 = caps->icmpv4;
+        p.caps_icmpv6 = caps->icmpv6;
+    }
+    p.dummy = ctx->dummy;
+    return p;
+}
+
+// launch() on the context's device; `what` names it in the error message.
+template <class F>
+int on_device(const smol_csum_ctx_t* ctx, const char* what, F&& launch) {
+    DeviceGuard guard(ctx->device);
+    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
+    const hipError_t e = launch();
+    return e == hipSuccess ? SMOL_OK : hip_fail(e, what);
+}
+
+// launch_records: a batch larger than that goes out as consecutive launches on the stream, each over the
+// next launch_records records.  launch(i0, q) launches the records from i0 on, q being p over them (n, and
+// desc or buf advanced); the caller's per-record arrays advance by i0.  Stops at the first failure.
+template <class F>
+hipError_t for_launches(const smol_csum_ctx_t* ctx, const smol_csum_batch_t* b, const KParams& p, F&& launch) {
+    const uint64_t per = ctx->launch_records && ctx->launch_records < b->n ? ctx->launch_records : b->n;
+    for (uint64_t i0 = 0; i0 < b->n; i0 += per) {
+        KParams q = p;
+        q.n = b->n - i0 < per ? b->n - i0 : per;
+        if (b->desc) q.desc = b->desc + i0;
+        else q.buf = p.buf + i0 * b->stride;
+        const hipError_t e = launch(i0, q);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 PickCtx pick_ctx(const smol_csum_ctx_t* ctx) { return {ctx->variant, ctx->shape, ctx->desc_staged}; }
 
 const char* family_kernel(int family) {
@@ -172,28 +241,14 @@ int run(smol_csum_ctx_t* ctx, int mode, uint8_t* d_buf, const smol_csum_batch_t*
         const smol_checksum_caps_t* caps, uint16_t* d_out, uint8_t* d_status, void* stream,
         const uint8_t* d_src = nullptr, const smol_csum_copy_t* d_copy = nullptr,
         const uint8_t* d_addrs = nullptr) {
-    KParams p;
-    std::memset(&p, 0, sizeof p);
+    KParams p = base_params(ctx, d_buf, b, caps);
     p.src = d_src;
     p.copy = d_copy;
-    p.buf = d_buf;
-    p.desc = b->desc;
-    p.n = b->n;
-    p.stride = b->stride;
-    p.len = b->len;
-    p.kind = d_addrs ? KIND_NHC_UDP : (b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u));
+    if (d_addrs) p.kind = KIND_NHC_UDP;
     p.addrs = d_addrs;
-    if (caps) {
-        p.caps_ipv4 = caps->ipv4;
-        p.caps_udp = caps->udp;
-        p.caps_tcp = caps->tcp;
-        p.caps_icmpv4 = caps->icmpv4;
-        p.caps_icmpv6 = caps->icmpv6;
-    }
     p.out16 = d_out;
     p.status = d_status;
-    p.dummy = ctx->dummy;
-    p.num_cu = ctx->max_blocks_set ? 0u : (uint32_t)(ctx->num_cu > 0 ? ctx->num_cu : 256);
+    p.num_cu = ctx->max_blocks_set ? 0u : cu_count(ctx);
     p.xcd_remap = ctx->xcd_remap >= 0 ? (uint32_t)ctx->xcd_remap : (uint32_t)xcd_remap_auto(mode, b);
     DeviceGuard guard(ctx->device);
     if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
@@ -373,17 +428,15 @@ int smol_csum_batch_data(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_
 
 int smol_csum_batch_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,
                          const smol_checksum_caps_t* caps, uint8_t* d_status, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK || b->n == 0) return rc;
+    int rc;
+    if (!begin_call(ctx, caps, b, d_buf, &rc)) return rc;
     return run(ctx, MODE_EMIT, d_buf, b, caps, nullptr, d_status, stream);
 }
 
 int smol_csum_batch_verify(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
                            const smol_checksum_caps_t* caps, uint8_t* d_status, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK || b->n == 0) return rc;
+    int rc;
+    if (!begin_call(ctx, caps, b, d_buf, &rc)) return rc;
     if (!d_status) return SMOL_EINVAL;
     return run(ctx, MODE_VERIFY, const_cast<uint8_t*>(d_buf), b, caps, nullptr, d_status, stream);
 }
@@ -391,9 +444,8 @@ int smol_csum_batch_verify(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smo
 int smol_csum_batch_copy_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,
                               const uint8_t* d_src, const smol_csum_copy_t* d_copy,
                               const smol_checksum_caps_t* caps, uint8_t* d_status, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK || b->n == 0) return rc;
+    int rc;
+    if (!begin_call(ctx, caps, b, d_buf, &rc)) return rc;
     if (!d_src || !d_copy || ((uintptr_t)d_copy & 15u) != 0) return SMOL_EINVAL;
     return run(ctx, MODE_COPY, d_buf, b, caps, nullptr, d_status, stream, d_src, d_copy);
 }
@@ -402,46 +454,25 @@ int smol_csum_batch_copy_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_c
 // Uses none of the context's scratch or events, so calls on different streams are independent.
 int smol_csum_batch_emit_fields(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
                                 const smol_checksum_caps_t* caps, smol_csum_fields_t* d_fields, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK || b->n == 0) return rc;
+    int rc;
+    if (!begin_call(ctx, caps, b, d_buf, &rc)) return rc;
     if (!d_fields || ((uintptr_t)d_fields & 15u) != 0) return SMOL_EINVAL;
-    KParams p;
-    std::memset(&p, 0, sizeof p);
-    p.buf = const_cast<uint8_t*>(d_buf);  // (the fields sink stores nothing there)
-    p.stride = b->stride;
-    p.len = b->len;
-    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
-    p.caps_ipv4 = caps->ipv4;
-    p.caps_udp = caps->udp;
-    p.caps_tcp = caps->tcp;
-    p.caps_icmpv4 = caps->icmpv4;
-    p.caps_icmpv6 = caps->icmpv6;
-    p.dummy = ctx->dummy;
-    p.num_cu = ctx->max_blocks_set ? 0u : (uint32_t)(ctx->num_cu > 0 ? ctx->num_cu : 256);
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
+    KParams p = base_params(ctx, d_buf, b, caps);  // (the fields sink stores nothing in d_buf)
+    p.num_cu = ctx->max_blocks_set ? 0u : cu_count(ctx);
     const hipStream_t s = (hipStream_t)stream;
-    // launch_records: consecutive launches, the entries advancing with the records
-    const uint64_t per = ctx->launch_records && ctx->launch_records < b->n ? ctx->launch_records : b->n;
-    for (uint64_t i0 = 0; i0 < b->n; i0 += per) {
-        p.n = b->n - i0 < per ? b->n - i0 : per;
-        p.desc = b->desc ? b->desc + i0 : nullptr;
-        if (!b->desc) p.buf = const_cast<uint8_t*>(d_buf) + i0 * b->stride;
-        p.fields = d_fields + i0;
-        hipError_t e;
-        switch (pick_fields(ctx->fields_kernel, b, p)) {
-            case FK_XWALK: e = launch_xwalk_fields(p, s); break;
-            case FK_DWALK: e = launch_dwalk_fields(p, s); break;
-            default:
-                // the walk kernel on variant 5's shape (kWalkVerify: the line grid)
-                e = b->desc ? launch_walk_fields<false>(auto_shape(b->len, true, kWalkVerify), p, ctx->max_blocks, s)
-                            : launch_walk_fields<true>(auto_shape(b->len, false, kWalkVerify), p, ctx->max_blocks, s);
-                break;
-        }
-        if (e != hipSuccess) return hip_fail(e, "emit_fields kernel launch");
-    }
-    return SMOL_OK;
+    return on_device(ctx, "emit_fields kernel launch", [&] {
+        return for_launches(ctx, b, p, [&](uint64_t i0, KParams q) {
+            q.fields = d_fields + i0;
+            switch (pick_fields(ctx->fields_kernel, b, q)) {
+                case FK_XWALK: return launch_xwalk_fields(q, s);
+                case FK_DWALK: return launch_dwalk_fields(q, s);
+                default: break;
+            }
+            // the walk kernel on variant 5's shape (kWalkVerify: the line grid)
+            return b->desc ? launch_walk_fields<false>(auto_shape(b->len, true, kWalkVerify), q, ctx->max_blocks, s)
+                           : launch_walk_fields<true>(auto_shape(b->len, false, kWalkVerify), q, ctx->max_blocks, s);
+        });
+    });
 }
 
 // Verify with the payloads delivered in the same pass (include/smolcsum.h).  Uses none of the context's
@@ -449,39 +480,20 @@ int smol_csum_batch_emit_fields(smol_csum_ctx_t* ctx, const uint8_t* d_buf, cons
 int smol_csum_batch_verify_copy(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
                                 const smol_checksum_caps_t* caps, uint8_t* d_dst, const smol_csum_slot_t* d_slots,
                                 uint8_t* d_status, smol_csum_span_t* d_spans, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK || b->n == 0) return rc;
+    int rc;
+    if (!begin_call(ctx, caps, b, d_buf, &rc)) return rc;
     if (!d_dst || !d_slots || !d_status || !d_spans || ((uintptr_t)d_slots & 15u) != 0 || ((uintptr_t)d_spans & 7u) != 0)
         return SMOL_EINVAL;
-    KParams p;
-    std::memset(&p, 0, sizeof p);
-    p.buf = const_cast<uint8_t*>(d_buf);  // (only read)
-    p.stride = b->stride;
-    p.len = b->len;
-    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
-    p.caps_ipv4 = caps->ipv4;
-    p.caps_udp = caps->udp;
-    p.caps_tcp = caps->tcp;
-    p.caps_icmpv4 = caps->icmpv4;
-    p.caps_icmpv6 = caps->icmpv6;
-    p.dummy = ctx->dummy;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
+    const KParams p = base_params(ctx, d_buf, b, caps);
     const hipStream_t s = (hipStream_t)stream;
     const int shape = ctx->shape >= 0 ? ctx->shape : vcopy_shape(b->len, b->desc != nullptr);
-    // launch_records: consecutive launches, the per-record arrays advancing with the records
-    const uint64_t per = ctx->launch_records && ctx->launch_records < b->n ? ctx->launch_records : b->n;
-    for (uint64_t i0 = 0; i0 < b->n; i0 += per) {
-        p.n = b->n - i0 < per ? b->n - i0 : per;
-        p.desc = b->desc ? b->desc + i0 : nullptr;
-        if (!b->desc) p.buf = const_cast<uint8_t*>(d_buf) + i0 * b->stride;
-        p.status = d_status + i0;
-        const VCopyArgs v = {d_dst, d_slots + i0, d_spans + i0};
-        const hipError_t e = launch_vcopy(shape, ctx->vcopy_nt, p, v, ctx->max_blocks, s);
-        if (e != hipSuccess) return hip_fail(e, "verify_copy kernel launch");
-    }
-    return SMOL_OK;
+    return on_device(ctx, "verify_copy kernel launch", [&] {
+        return for_launches(ctx, b, p, [&](uint64_t i0, KParams q) {
+            q.status = d_status + i0;
+            const VCopyArgs v = {d_dst, d_slots + i0, d_spans + i0};
+            return launch_vcopy(shape, ctx->vcopy_nt, q, v, ctx->max_blocks, s);
+        });
+    });
 }
 
 // ---- IPv4 fragment groups ---------------------------------------------------------------------
@@ -489,31 +501,12 @@ int smol_csum_batch_verify_copy(smol_csum_ctx_t* ctx, const uint8_t* d_buf, cons
 static int run_frag(smol_csum_ctx_t* ctx, int mode, uint8_t* d_buf, const smol_csum_batch_t* b,
                     const smol_csum_frag_group_t* d_groups, uint64_t n_groups, const smol_checksum_caps_t* caps,
                     uint8_t* d_status, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK) return rc;
-    if (n_groups == 0) return SMOL_OK;
-    if (b->n == 0 || !d_groups || ((uintptr_t)d_groups & 15u) != 0) return SMOL_EINVAL;
+    int rc;
+    if (!begin_group_call(ctx, caps, b, d_buf, d_groups, n_groups, &rc)) return rc;
     if (mode == MODE_VERIFY && !d_status) return SMOL_EINVAL;
-    KParams p;
-    std::memset(&p, 0, sizeof p);
-    p.buf = d_buf;
-    p.desc = b->desc;
-    p.n = b->n;
-    p.stride = b->stride;
-    p.len = b->len;
-    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
-    p.caps_ipv4 = caps->ipv4;
-    p.caps_udp = caps->udp;
-    p.caps_tcp = caps->tcp;
-    p.caps_icmpv4 = caps->icmpv4;
-    p.caps_icmpv6 = caps->icmpv6;
+    KParams p = base_params(ctx, d_buf, b, caps);
     p.status = d_status;
-    p.dummy = ctx->dummy;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
-    hipError_t e = launch_frag(mode, p, d_groups, n_groups, (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "fragment kernel launch");
+    return on_device(ctx, "fragment kernel launch", [&] { return launch_frag(mode, p, d_groups, n_groups, (hipStream_t)stream); });
 }
 
 int smol_csum_batch_emit_frag(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,
@@ -535,33 +528,15 @@ int smol_csum_batch_verify_reassemble(smol_csum_ctx_t* ctx, const uint8_t* d_buf
                                       const smol_csum_frag_group_t* d_groups, uint64_t n_groups,
                                       const smol_checksum_caps_t* caps, uint8_t* d_dst, const smol_csum_slot_t* d_slots,
                                       uint8_t* d_status, smol_csum_dgram_t* d_dgrams, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK) return rc;
-    if (n_groups == 0) return SMOL_OK;
-    if (b->n == 0 || !d_groups || ((uintptr_t)d_groups & 15u) != 0) return SMOL_EINVAL;
+    int rc;
+    if (!begin_group_call(ctx, caps, b, d_buf, d_groups, n_groups, &rc)) return rc;
     if (!d_dst || !d_slots || !d_status || !d_dgrams || ((uintptr_t)d_slots & 15u) != 0 || ((uintptr_t)d_dgrams & 15u) != 0)
         return SMOL_EINVAL;
-    KParams p;
-    std::memset(&p, 0, sizeof p);
-    p.buf = const_cast<uint8_t*>(d_buf);  // (only read)
-    p.desc = b->desc;
-    p.n = b->n;
-    p.stride = b->stride;
-    p.len = b->len;
-    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
-    p.caps_ipv4 = caps->ipv4;
-    p.caps_udp = caps->udp;
-    p.caps_tcp = caps->tcp;
-    p.caps_icmpv4 = caps->icmpv4;
-    p.caps_icmpv6 = caps->icmpv6;
+    KParams p = base_params(ctx, d_buf, b, caps);
     p.status = d_status;
-    p.dummy = ctx->dummy;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
     const FragCopyArgs v = {d_dst, d_slots, d_dgrams};
-    const hipError_t e = launch_fragcopy(p, d_groups, n_groups, v, (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "verify_reassemble kernel launch");
+    return on_device(ctx, "verify_reassemble kernel launch",
+                     [&] { return launch_fragcopy(p, d_groups, n_groups, v, (hipStream_t)stream); });
 }
 
 // Emit with every whole IPv4 datagram cut into frames in its place of d_dst in the same pass
@@ -570,29 +545,12 @@ int smol_csum_batch_verify_reassemble(smol_csum_ctx_t* ctx, const uint8_t* d_buf
 int smol_csum_batch_fragment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
                                   const smol_checksum_caps_t* caps, uint8_t* d_dst, const smol_csum_fragplan_t* d_plans,
                                   uint32_t frame_stride, smol_csum_fragout_t* d_out, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK || b->n == 0) return rc;
+    int rc;
+    if (!begin_call(ctx, caps, b, d_buf, &rc)) return rc;
     if (!d_dst || !d_plans || !d_out || ((uintptr_t)d_plans & 15u) != 0 || ((uintptr_t)d_out & 15u) != 0) return SMOL_EINVAL;
-    KParams p;
-    std::memset(&p, 0, sizeof p);
-    p.buf = const_cast<uint8_t*>(d_buf);  // (only read)
-    p.desc = b->desc;
-    p.n = b->n;
-    p.stride = b->stride;
-    p.len = b->len;
-    p.kind = b->kind | ((b->flags & SMOL_REC_IPHDR_ONLY) ? KIND_IPHDR_ONLY : 0u);
-    p.caps_ipv4 = caps->ipv4;
-    p.caps_udp = caps->udp;
-    p.caps_tcp = caps->tcp;
-    p.caps_icmpv4 = caps->icmpv4;
-    p.caps_icmpv6 = caps->icmpv6;
-    p.dummy = ctx->dummy;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
+    const KParams p = base_params(ctx, d_buf, b, caps);
     const FragCutArgs v = {d_dst, d_plans, frame_stride, d_out};
-    const hipError_t e = launch_fragcut(p, v, (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "fragment_emit kernel launch");
+    return on_device(ctx, "fragment_emit kernel launch", [&] { return launch_fragcut(p, v, (hipStream_t)stream); });
 }
 
 // ---- 6LoWPAN NHC UDP --------------------------------------------------------------------------
@@ -600,9 +558,8 @@ int smol_csum_batch_fragment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf, co
 int smol_csum_batch_nhc_udp_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,
                                  const smol_ipv6_addr_pair_t* d_addrs, const smol_checksum_caps_t* caps,
                                  uint8_t* d_status, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK || b->n == 0) return rc;
+    int rc;
+    if (!begin_call(ctx, caps, b, d_buf, &rc)) return rc;
     if (!d_addrs || ((uintptr_t)d_addrs & 3u) != 0) return SMOL_EINVAL;
     return run(ctx, MODE_EMIT, d_buf, b, caps, nullptr, d_status, stream, nullptr, nullptr,
                reinterpret_cast<const uint8_t*>(d_addrs));
@@ -611,9 +568,8 @@ int smol_csum_batch_nhc_udp_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smo
 int smol_csum_batch_nhc_udp_verify(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
                                    const smol_ipv6_addr_pair_t* d_addrs, const smol_checksum_caps_t* caps,
                                    uint8_t* d_status, void* stream) {
-    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
-    int rc = check_batch(b, d_buf);
-    if (rc != SMOL_OK || b->n == 0) return rc;
+    int rc;
+    if (!begin_call(ctx, caps, b, d_buf, &rc)) return rc;
     if (!d_status || !d_addrs || ((uintptr_t)d_addrs & 3u) != 0) return SMOL_EINVAL;
     return run(ctx, MODE_VERIFY, const_cast<uint8_t*>(d_buf), b, caps, nullptr, d_status, stream, nullptr,
                nullptr, reinterpret_cast<const uint8_t*>(d_addrs));
@@ -631,10 +587,9 @@ int smol_csum_tool_synth(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_b
     int rc = check_batch(b, d_buf);
     if (rc != SMOL_OK || b->n == 0) return rc;
     SynthParams p{d_buf, b->desc, b->n, b->stride, b->len, (uint32_t)profile, seed};
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
-    hipError_t e = launch_synth(p, ctx->max_blocks, (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "synth kernel launch");
+    return on_device(ctx, "synth kernel launch", [&] {
+        return launch_synth(p, ctx->max_blocks, (hipStream_t)stream);
+    });
 }
 
 int smol_csum_tool_corrupt(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,
@@ -643,10 +598,9 @@ int smol_csum_tool_corrupt(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum
     int rc = check_batch(b, d_buf);
     if (rc != SMOL_OK || b->n == 0) return rc;
     SynthParams p{d_buf, b->desc, b->n, b->stride, b->len, 0u, seed};
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
-    hipError_t e = launch_corrupt(p, every, (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "corrupt kernel launch");
+    return on_device(ctx, "corrupt kernel launch", [&] {
+        return launch_corrupt(p, every, (hipStream_t)stream);
+    });
 }
 
 int smol_csum_tool_set_shape(smol_csum_ctx_t* ctx, int shape) {
@@ -703,32 +657,26 @@ int smol_csum_tool_set_vcopy_stores(smol_csum_ctx_t* ctx, int nt) {
 int smol_csum_tool_stream_read(smol_csum_ctx_t* ctx, const uint8_t* d_buf, uint64_t bytes,
                                uint32_t* d_sink, void* stream) {
     if (!ctx || !d_buf || !d_sink || (bytes & 15u) || ((uintptr_t)d_buf & 15u)) return SMOL_EINVAL;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
-    hipError_t e = launch_stream_read(d_buf, bytes, d_sink, (uint32_t)(ctx->num_cu > 0 ? ctx->num_cu : 256) * 8u,
-                                      (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "stream-read kernel launch");
+    return on_device(ctx, "stream-read kernel launch", [&] {
+        return launch_stream_read(d_buf, bytes, d_sink, cu_count(ctx) * 8u, (hipStream_t)stream);
+    });
 }
 
 int smol_csum_tool_field_probe(smol_csum_ctx_t* ctx, uint8_t* d_buf, uint64_t bytes, uint64_t stride,
                                uint32_t f1, uint32_t f2, void* stream) {
     if (!ctx || !d_buf || (bytes & 15u) || ((uintptr_t)d_buf & 15u) || stride == 0 || f1 == ~0u) return SMOL_EINVAL;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
-    hipError_t e = launch_field_probe(d_buf, bytes, stride, f1, f2, (uint32_t)(ctx->num_cu > 0 ? ctx->num_cu : 256) * 8u,
-                                      (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "field-probe kernel launch");
+    return on_device(ctx, "field-probe kernel launch", [&] {
+        return launch_field_probe(d_buf, bytes, stride, f1, f2, cu_count(ctx) * 8u, (hipStream_t)stream);
+    });
 }
 
 int smol_csum_tool_field_probe_list(smol_csum_ctx_t* ctx, uint8_t* d_buf, uint64_t bytes, const uint64_t* d_addrs,
                                     const uint32_t* d_piece_first, int flags, void* stream) {
     if (!ctx || !d_buf || !d_addrs || !d_piece_first || (bytes & 15u) || ((uintptr_t)d_buf & 15u) || (flags & ~1))
         return SMOL_EINVAL;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
-    hipError_t e = launch_field_probe_list(d_buf, bytes, d_addrs, d_piece_first, flags & 1,
-                                           (uint32_t)(ctx->num_cu > 0 ? ctx->num_cu : 256) * 8u, (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "field-probe kernel launch");
+    return on_device(ctx, "field-probe kernel launch", [&] {
+        return launch_field_probe_list(d_buf, bytes, d_addrs, d_piece_first, flags & 1, cu_count(ctx) * 8u, (hipStream_t)stream);
+    });
 }
 
 int smol_csum_tool_segment_probe(smol_csum_ctx_t* ctx, uint8_t* d_buf, uint64_t bytes, const uint32_t* d_bitmap, int flags,
@@ -736,20 +684,17 @@ int smol_csum_tool_segment_probe(smol_csum_ctx_t* ctx, uint8_t* d_buf, uint64_t 
     if (!ctx || !d_buf || !d_bitmap || (bytes & 15u) || ((uintptr_t)d_buf & 15u) || ((uintptr_t)d_bitmap & 15u) ||
         (flags & ~1))
         return SMOL_EINVAL;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
-    hipError_t e = launch_segment_probe(d_buf, bytes, d_bitmap, flags & 1, (uint32_t)(ctx->num_cu > 0 ? ctx->num_cu : 256) * 8u,
-                                        (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "segment-probe kernel launch");
+    return on_device(ctx, "segment-probe kernel launch", [&] {
+        return launch_segment_probe(d_buf, bytes, d_bitmap, flags & 1, cu_count(ctx) * 8u, (hipStream_t)stream);
+    });
 }
 
 int smol_csum_tool_field_scatter(smol_csum_ctx_t* ctx, uint8_t* d_buf, uint64_t bytes, const uint64_t* d_addrs,
                                  const uint16_t* d_vals, uint64_t n, int flags, void* stream) {
     if (!ctx || !d_buf || (n && (!d_addrs || !d_vals)) || (flags & ~15) || n > (0xFFFFFFull << 8)) return SMOL_EINVAL;
-    DeviceGuard guard(ctx->device);
-    if (!guard.ok) return hip_fail(hipErrorInvalidDevice, "hipSetDevice");
-    hipError_t e = launch_field_scatter(d_buf, bytes, d_addrs, d_vals, n, flags & 15, (hipStream_t)stream);
-    return e == hipSuccess ? SMOL_OK : hip_fail(e, "field-scatter kernel launch");
+    return on_device(ctx, "field-scatter kernel launch", [&] {
+        return launch_field_scatter(d_buf, bytes, d_addrs, d_vals, n, flags & 15, (hipStream_t)stream);
+    });
 }
 
 int smol_csum_tool_auto_shape(uint32_t len, int has_desc) {

@@ -15,14 +15,12 @@
 //      byte, the L4 span and the offsets of the fields emit writes are emit's by construction.  The cut
 //      (count, frame lengths) and the cap / stride test follow; a datagram that is not cut or does not fit
 //      streams nothing.
-//   2. Streaming.  The wave walks the frames in order.  A frame's payload slice is streamed as 16-B chunks
-//      on the source's grid, U per lane and step, all loads of a step issued first, and the first step of
-//      the NEXT frame is issued before the current one is used.  Each chunk is summed as aligned words
-//      (edges masked, UDP capped at its length field: the tail is delivered, not summed) and funnelled
-//      onto the destination's 16-B grid exactly as fragcopy does (funnel16 of chunk slot k and its
-//      successor, taken from the next lane; lane 63's from one extra load).  The shift is per frame: the
-//      frame length is 2 or 4 mod 8.  Chunks entirely inside the slice go out as one dwordx4 store, a
-//      slice's first and last chunk byte-masked (store_edge).
+//   2. Streaming.  The wave walks the frames in order.  A frame's payload slice is streamed as a
+//      vcopy::Piece (csum_walk.h, fragcopy's streamer), U chunks per lane and step, all loads of a step
+//      issued first, and the first step of the NEXT frame is issued before the current one is used.  Each
+//      chunk is summed as aligned words (edges masked, UDP capped at its length field: the tail is
+//      delivered, not summed) and funnelled onto the destination's 16-B grid.  The shift is per frame: the
+//      frame length is 2 or 4 mod 8.
 //   3. Frame head.  Lane i < io + 20 holds byte i of the record's headers; per frame it substitutes total
 //      length, ident, flags / offset and the header checksum (computed by every lane from the six words
 //      that do not change: a 10-word sum) and stores its byte.
@@ -33,41 +31,43 @@
 //      nothing depends on the order of two stores.  step is a multiple of 8 and the offsets are even, so
 //      a field never straddles two frames.
 // No byte of d_dst is read.
-#include "csum_walk.h"
+#include "csum_fraggroup.h"
 
 namespace smolcsum {
 namespace fragcut {
+
+using fraggroup::rb;
+using fraggroup::rb16;
 
 constexpr int U = 2;  // chunks per lane and step: a 1480-B slice is one step
 constexpr uint32_t STEP = 64 * U;
 constexpr int32_t NO_HOLD = -(1 << 30);
 
-__device__ __forceinline__ uint32_t rb(uint64_t a) { return *(gcu8)a; }
-__device__ __forceinline__ uint32_t rb16(uint64_t a) { return (rb(a) << 8) | rb(a + 1); }
+// One frame: its payload slice (the same for every lane of the wave) and what the frame head needs.
+struct Frame {
+    vcopy::Piece<false> q;  // the slice: all of it delivered, its bytes below the L4 span's end summed
+    uint64_t F;      // destination address of the frame's first byte
+    uint32_t lo;     // datagram-payload offset of the slice
+    int32_t h0, h1;  // slice-relative offsets of the held-back fields (far below 0: none)
+    uint32_t more;   // another frame follows (MF)
+};
 
-// One frame's payload slice (the same for every lane of the wave).
-struct Piece {
-    uint64_t base;     // chunk-grid origin: the slice's source address rounded down to 16
-    uint64_t D;        // destination address of the slice's first byte
-    uint64_t F;        // destination address of the frame's first byte
-    uint32_t head;     // source address - base
-    uint32_t nch;      // source chunks that hold a byte of the slice
-    uint32_t lead;     // 1: the chunk slots start one chunk before base (slot k holds chunk k - lead)
-    uint32_t nk;       // chunk slots: nch + lead
-    uint32_t sh;       // funnel shift: (head - dh) mod 16
-    uint32_t dh;       // D mod 16
-    uint32_t lo;       // datagram-payload offset of the slice
-    uint32_t sum_len;  // slice bytes summed (0: none)
-    uint32_t copy_len; // slice bytes delivered
-    int32_t h0, h1;    // slice-relative offsets of the held-back fields (far below 0: none)
-    uint32_t more;     // another frame follows (MF)
+// A held-back field in a destination chunk (at most one: they lie 16 apart): the bytes around it go out.
+struct HeldBack {
+    int32_t h0, h1;
+    __device__ __forceinline__ bool operator()(gu8 dst, const u32x4& m, int pos, int lo, int end) const {
+        const int a = max(lo, 0), b = min(end, 16);
+        int h = h0 - pos;
+        if (!(h + 2 > a && h < b)) h = h1 - pos;
+        if (!(h + 2 > a && h < b)) return false;
+        vcopy::store_edge(dst, m, a, h);
+        vcopy::store_edge(dst, m, h + 2, b);
+        return true;
+    }
 };
 
 template <bool IMPLICIT>
 __global__ __launch_bounds__(256) void fragcut_kernel(KParams p, FragCutArgs v) {
-    using vcopy::next4;
-    using vcopy::store_edge;
-    using vcopy::sum_chunk;
     const int lane = (int)(threadIdx.x & 63u);
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint64_t dummy = (uint64_t)p.dummy;
@@ -75,20 +75,10 @@ __global__ __launch_bounds__(256) void fragcut_kernel(KParams p, FragCutArgs v) 
 
     for (uint64_t r = 4ull * blockIdx.x + wave; r < p.n; r += nwaves) {
         // ---- 1. the gate: emit's parse, the cut, the cap ----
-        uint64_t a0;
-        uint32_t len, kind;
-        if (IMPLICIT) {
-            a0 = (uint64_t)p.buf + r * p.stride;
-            len = p.len;
-            kind = p.kind;
-        } else {
-            const u32x4 d = *(gcv4)((uint64_t)p.desc + 16 * r);
-            a0 = (uint64_t)p.buf + ((uint64_t)d.x | ((uint64_t)d.y << 32));
-            len = d.z;
-            kind = desc_kind(d.w);
-        }
+        const RecRef rr = rec_at<IMPLICIT, false>(p, r);
+        const uint64_t a0 = rr.a0;
         auto rd = [&](uint32_t o) -> uint32_t { return rb(a0 + o); };
-        const Geom g = parse_geometry<false>(rd, len, kind, true);
+        const Geom g = parse_geometry<false>(rd, rr.len, rr.kind, true);
         const u32x4 pl = *(gcv4)((uint64_t)v.plans + 16ull * r);  // dst_offset, cap, ip_mtu | ident << 16
         const uint32_t cap = pl.z, mtu = pl.w & 0xffffu, ident = pl.w >> 16;
         const uint32_t io = g.ip_off, l4o = io + 20;
@@ -125,102 +115,47 @@ __global__ __launch_bounds__(256) void fragcut_kernel(KParams p, FragCutArgs v) 
             const uint32_t hb = rb(a0 + ((uint32_t)lane < l4o ? (uint32_t)lane : 0u));
             const uint32_t H0 = rb16(ip) + rb16(ip + 8) + rb16(ip + 12) + rb16(ip + 14) + rb16(ip + 16) + rb16(ip + 18);
 
-            auto setup = [&](uint32_t k) -> Piece {
-                Piece q;
-                q.lo = k * pstep;
-                const uint32_t hi = min(q.lo + pstep, T);
-                const uint64_t A = a0 + l4o + q.lo;
-                q.copy_len = hi - q.lo;
-                q.sum_len = span > q.lo ? min(span, hi) - q.lo : 0u;
-                q.base = A & ~15ull;
-                q.head = (uint32_t)(A - q.base);
-                q.nch = q.copy_len ? (uint32_t)(((A + q.copy_len + 15) >> 4) - (q.base >> 4)) : 0u;
-                q.F = Dbase + (uint64_t)k * S;
-                q.D = q.F + l4o;
-                q.dh = (uint32_t)(q.D & 15u);
-                q.sh = (q.head - q.dh) & 15u;
-                q.lead = q.copy_len && q.head < q.dh ? 1u : 0u;
-                q.nk = q.nch + q.lead;
-                q.h0 = f1 - (int32_t)q.lo;
-                q.h1 = f2 - (int32_t)q.lo;
-                q.more = k + 1 < count;
-                return q;
-            };
-            // one step: chunk slots [i0, i0 + STEP), and for lane 63 the slot after them
-            auto load = [&](const Piece& q, uint32_t i0, u32x4 (&c)[U], u32x4& xh) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const uint32_t k = i0 + (uint32_t)(u * 64 + lane) - q.lead;  // (slot 0 of a lead: wraps, >= nch)
-                    c[u] = ld16<false>((gcv4)(k < q.nch ? q.base + 16ull * k : dummy));
-                }
-                const uint32_t kx = i0 + STEP - q.lead;
-                xh = ld16<false>((gcv4)(lane == 63 && kx < q.nch ? q.base + 16ull * kx : dummy));
-            };
-            auto use = [&](const Piece& q, uint32_t i0, const u32x4 (&c)[U], const u32x4& xh, uint32_t& acc) {
-                if (q.sum_len) {
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        const uint32_t k = i0 + (uint32_t)(u * 64 + lane) - q.lead;
-                        if (k < q.nch) acc = sum_chunk(c[u], (int)(16u * k) - (int)q.head, (int)q.sum_len, acc);
-                    }
-                }
-                // (the wave's lanes together: the exchange below needs all of them)
-                u32x4 ncur = next4<64>(c[0], lane);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const u32x4 nnext = u + 1 < U ? next4<64>(c[u + 1 < U ? u + 1 : u], lane) : xh;
-                    const u32x4 hi = lane == 63 ? nnext : ncur;
-                    ncur = nnext;
-                    const uint32_t k = i0 + (uint32_t)(u * 64 + lane);
-                    const int pos = (int)(16u * k) - (int)q.dh;  // slice-relative start of destination chunk k
-                    const int lo = -pos, end = (int)q.copy_len - pos;
-                    if (k < q.nk && end > 0 && lo < 16) {
-                        const u32x4 m = funnel16(c[u], hi, q.sh);
-                        const gu8 dst = (gu8)(q.D + (uint64_t)(int64_t)pos);
-                        const int a = max(lo, 0), b = min(end, 16);
-                        // a held-back field in this chunk (at most one: they lie 16 apart): the bytes around it
-                        int h = q.h0 - pos;
-                        if (!(h + 2 > a && h < b)) h = q.h1 - pos;
-                        if (h + 2 > a && h < b) {
-                            store_edge(dst, m, a, h);
-                            store_edge(dst, m, h + 2, b);
-                        } else if (lo <= 0 && end >= 16) {
-                            *(GMEM u32x4*)dst = m;
-                        } else {
-                            store_edge(dst, m, lo, end);
-                        }
-                    }
-                }
+            auto setup = [&](uint32_t k) -> Frame {
+                Frame f;
+                f.lo = k * pstep;
+                const uint32_t hi = min(f.lo + pstep, T);
+                f.F = Dbase + (uint64_t)k * S;
+                f.q = vcopy::Piece<false>(a0 + l4o + f.lo, f.F + l4o, span > f.lo ? min(span, hi) - f.lo : 0u, hi - f.lo);
+                f.h0 = f1 - (int32_t)f.lo;
+                f.h1 = f2 - (int32_t)f.lo;
+                f.more = k + 1 < count;
+                return f;
             };
             // the io + 20 header bytes of the frame, one byte per lane
-            auto head = [&](const Piece& q) {
-                const uint32_t tl = 20 + q.copy_len;
+            auto head = [&](const Frame& f) {
+                const uint32_t tl = 20 + f.q.copy_len;
                 const uint32_t idk = single ? id0 : ident;
-                const uint32_t flk = single ? fl0 : ((q.more ? 0x2000u : 0u) | (q.lo >> 3));
+                const uint32_t flk = single ? fl0 : ((f.more ? 0x2000u : 0u) | (f.lo >> 3));
                 const uint32_t cs = caps_tx(p.caps_ipv4) ? (~fold32(H0 + tl + idk + flk) & 0xffffu) : 0u;
                 const int j = lane - (int)io;
                 const uint32_t b = j == 2 ? tl >> 8 : j == 3 ? tl : j == 4 ? idk >> 8 : j == 5 ? idk
                                  : j == 6 ? flk >> 8 : j == 7 ? flk : j == 10 ? cs >> 8 : j == 11 ? cs : hb;
-                if ((uint32_t)lane < l4o) ((gu8)q.F)[lane] = (uint8_t)b;
+                if ((uint32_t)lane < l4o) ((gu8)f.F)[lane] = (uint8_t)b;
             };
 
             uint32_t acc = 0;  // this lane's part of the aligned-word sum over the summed payload bytes
             {
-                Piece cur = setup(0u);
+                Frame cur = setup(0u);
                 u32x4 c[U], xh;
-                load(cur, 0u, c, xh);
+                vcopy::piece_load<U>(cur.q, 0u, lane, dummy, c, xh);
                 for (uint32_t k = 0; k < count; ++k) {
-                    Piece nxt = {};
+                    Frame nxt = {};
                     u32x4 cn[U], xn;
                     if (k + 1 < count) {  // the next frame's first step, in flight under this one's work
                         nxt = setup(k + 1);
-                        load(nxt, 0u, cn, xn);
+                        vcopy::piece_load<U>(nxt.q, 0u, lane, dummy, cn, xn);
                     }
                     head(cur);
-                    use(cur, 0u, c, xh, acc);
-                    for (uint32_t i0 = STEP; i0 < cur.nk; i0 += STEP) {
-                        load(cur, i0, c, xh);
-                        use(cur, i0, c, xh, acc);
+                    const HeldBack hold = {cur.h0, cur.h1};
+                    vcopy::piece_use<U>(cur.q, 0u, lane, c, xh, acc, hold);
+                    for (uint32_t i0 = STEP; i0 < cur.q.nk; i0 += STEP) {
+                        vcopy::piece_load<U>(cur.q, i0, lane, dummy, c, xh);
+                        vcopy::piece_use<U>(cur.q, i0, lane, c, xh, acc, hold);
                     }
                     cur = nxt;
 #pragma unroll

@@ -362,7 +362,8 @@ __device__ __forceinline__ uint32_t sum_masked_words(const u32x4& c, int lo, int
     return add_words(mask_dword(c.w, lo - 12, hi - 12), acc);
 }
 
-// The sum-and-deliver kernels' chunk helpers (csum_vcopy.hip, csum_fragcopy.hip).
+// The sum-and-deliver kernels' chunk helpers (csum_vcopy.hip) and, for the kernels that stream one piece
+// after the other with a whole wave (csum_fragcopy.hip, csum_fragcut.hip), the piece streamer.
 namespace vcopy {
 
 // The chunk the next lane of the group holds (lane G - 1: lane 0's).
@@ -389,6 +390,101 @@ __device__ __forceinline__ void store_edge(gu8 dst, const u32x4& c, int lo, int 
     const uint32_t cw[4] = {c.x, c.y, c.z, c.w};
 #pragma unroll
     for (int i = 0; i < 4; ++i) store_dword_masked(dst + 4 * i, cw[i], byte_mask(lo, hi, i));
+}
+
+// One piece of a 64-lane wave's stream (the same for every lane): contiguous source bytes, of which the
+// first sum_len are summed and the first copy_len delivered to contiguous destination bytes.  Its 16-B
+// chunks lie on the source's grid, destination chunks on the destination's: destination chunk k (piece
+// bytes [16 k - dh, 16 k - dh + 16)) is funnel16 of chunk slot k and its successor.  When dh is larger
+// than the source's offset in its first chunk, the slots start one chunk early (slot 0 reads the dummy
+// line: none of its bytes is used).
+// SUM_ONLY: the kernel has pieces that are summed and not delivered (fragcopy_kernel: a group over its
+// cap), so the streamed range is the longer of the two, and a piece with copy_len 0 skips the exchange
+// and lane 63's extra load.  A kernel that sums no byte it does not deliver (fragcut_kernel) would get
+// the same results from these tests: with copy_len 0 its nch and nk are 0, nothing loads or stores either
+// way.  It is spared them because they cost it 1.2 % (fragment_emit with them against without, three
+// shapes, interleaved on one MI355X: 0.1076 / 0.1037, 0.1424 / 0.1398, 0.1916 / 0.1892 ms).
+template <bool SUM_ONLY>
+struct Piece {
+    uint64_t base;     // chunk-grid origin: the source address rounded down to 16
+    uint64_t D;        // destination address of the piece's first byte
+    uint32_t head;     // source address - base
+    uint32_t nch;      // source chunks that hold a byte of the streamed range
+    uint32_t lead;     // 1: the chunk slots start one chunk before base (slot k holds chunk k - lead)
+    uint32_t nk;       // chunk slots: nch + lead
+    uint32_t sh;       // funnel shift: (head - dh) mod 16
+    uint32_t dh;       // D mod 16
+    uint32_t sum_len;  // bytes summed (0: none)
+    uint32_t copy_len; // bytes delivered (0: none)
+    Piece() = default;
+    __device__ __forceinline__ Piece(uint64_t A, uint64_t D_, uint32_t sum_len_, uint32_t copy_len_) {
+        sum_len = sum_len_;
+        copy_len = copy_len_;
+        const uint32_t L = SUM_ONLY ? max(sum_len, copy_len) : copy_len;
+        base = A & ~15ull;
+        head = (uint32_t)(A - base);
+        nch = L ? (uint32_t)(((A + L + 15) >> 4) - (base >> 4)) : 0u;
+        D = D_;
+        dh = (uint32_t)(D & 15u);
+        sh = (head - dh) & 15u;
+        lead = copy_len && head < dh ? 1u : 0u;
+        nk = nch + lead;
+    }
+    __device__ __forceinline__ bool odd() const { return (head & 1u) != 0; }  // the source address is odd
+    __device__ __forceinline__ bool delivers() const { return !SUM_ONLY || copy_len != 0; }
+};
+
+// The loads of one step, U chunks per lane: chunk slots [i0, i0 + 64 U), and for lane 63 the slot after
+// them (xh).  All of them issued unconditionally; what does not exist reads the dummy line.
+template <int U, bool SO>
+__device__ __forceinline__ void piece_load(const Piece<SO>& q, uint32_t i0, int lane, uint64_t dummy, u32x4 (&c)[U], u32x4& xh) {
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+        const uint32_t k = i0 + (uint32_t)(u * 64 + lane) - q.lead;  // (slot 0 of a lead: wraps, >= nch)
+        c[u] = ld16<false>((gcv4)(k < q.nch ? q.base + 16ull * k : dummy));
+    }
+    const uint32_t kx = i0 + 64u * U - q.lead;
+    xh = ld16<false>((gcv4)(q.delivers() && lane == 63 && kx < q.nch ? q.base + 16ull * kx : dummy));
+}
+
+// Nothing of a destination chunk is held back.
+struct NoHold {
+    __device__ __forceinline__ bool operator()(gu8, const u32x4&, int, int, int) const { return false; }
+};
+
+// One step's work: each chunk summed (edges masked) into acc, and the destination chunks stored: those
+// entirely inside the piece as one dwordx4 store, the piece's first and last chunk byte-masked
+// (store_edge).  hold(dst, m, pos, lo, end) may store chunk m itself (piece bytes [pos, pos + 16), of
+// which chunk bytes [lo, end) belong to the piece) and return true: csum_fragcut.hip's held-back fields.
+template <int U, bool SO, class HOLD>
+__device__ __forceinline__ void piece_use(const Piece<SO>& q, uint32_t i0, int lane, const u32x4 (&c)[U], const u32x4& xh,
+                                          uint32_t& acc, const HOLD& hold) {
+    if (q.sum_len) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const uint32_t k = i0 + (uint32_t)(u * 64 + lane) - q.lead;
+            if (k < q.nch) acc = sum_chunk(c[u], (int)(16u * k) - (int)q.head, (int)q.sum_len, acc);
+        }
+    }
+    if (q.delivers()) {  // (the wave's lanes together: the exchange below needs all of them)
+        u32x4 ncur = next4<64>(c[0], lane);
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const u32x4 nnext = u + 1 < U ? next4<64>(c[u + 1 < U ? u + 1 : u], lane) : xh;
+            const u32x4 hi = lane == 63 ? nnext : ncur;
+            ncur = nnext;
+            const uint32_t k = i0 + (uint32_t)(u * 64 + lane);
+            const int pos = (int)(16u * k) - (int)q.dh;  // piece-relative start of destination chunk k
+            const int lo = -pos, end = (int)q.copy_len - pos;
+            if (k < q.nk && end > 0 && lo < 16) {
+                const u32x4 m = funnel16(c[u], hi, q.sh);
+                const gu8 dst = (gu8)(q.D + (uint64_t)(int64_t)pos);
+                if (hold(dst, m, pos, lo, end)) continue;
+                if (lo <= 0 && end >= 16) *(GMEM u32x4*)dst = m;
+                else store_edge(dst, m, lo, end);
+            }
+        }
+    }
 }
 
 }  // namespace vcopy

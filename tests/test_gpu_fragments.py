@@ -149,6 +149,23 @@ def test_group_emit_drop_in_route(eng, mtu, eth):
     assert (vst & E.ST_ACCEPT).all()
 
 
+def test_group_emit_more_than_64_fragments(eng):
+    """Groups of more than 64 fragments: a lane of frag_kernel's emit takes a second and a fourth fragment.
+    An IP MTU of 28 leaves 8 payload bytes per fragment: 12 groups of 77 to 225 fragments (UDP, TCP, ICMP
+    echo, the ICMPv4 error, whose embedded-header field lies in fragment 2 as TCP's field does), and one
+    group of exactly SMOL_MAX_FRAGMENTS = 256."""
+    rng = np.random.default_rng(3)
+    dg = F.datagrams(rng, 12, 512, 2040)
+    dg.append(P.ipv4(F.A, F.B, 17, P.udp(5099, 53, P.rand_bytes(rng, 2040)), flags_frag=0x4000))
+    off, ref, groups = F.tx_pair(dg, 28, False, shuffle_rng=rng)
+    counts = [c for _, c in groups]
+    assert min(counts) == 77 and max(counts[:12]) == 225 and sum(counts[:12]) == 1971 and counts[12] == 256
+    got, offs, lens, vst = _device_frag(eng, off, groups, E.KIND_IP, seed=28)
+    for o, ln, want in zip(offs, lens, ref):
+        assert got[int(o):int(o) + int(ln)].tobytes() == want
+    assert (vst & E.ST_ACCEPT).all()
+
+
 def test_group_caps_and_one_record_groups(eng):
     """Every caps row; groups of one unfragmented packet mixed with fragmented datagrams."""
     rng = np.random.default_rng(11)
