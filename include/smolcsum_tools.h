@@ -162,11 +162,12 @@ int smol_csum_tool_variant_info(int variant, int out[4]);
  * (the rest 0).  Read through the switch the launchers instantiate their kernels with.  SMOL_EINVAL: not
  * such a variant, or it has no form of that op. */
 int smol_csum_tool_form(int variant, int op, int out[13]);
-/* The walk kernel (csum_kernel) that a launch of `variant` would run for `op` (0 data, 1 emit, 2 verify,
- * 3 copy-emit) over a fixed-stride (`implicit` != 0) or descriptor batch, a 6LoWPAN NHC batch when `nhc`,
- * at launch shape `shape` (0-8): out = {kernel id (1 walk, 4 NHC walk), the variant reported to
- * smol_csum_tool_last_launch, G, U}.  Read from the switch and the shape mapper the launcher runs; it
- * launches nothing.  SMOL_EINVAL: the walk kernel has no launch for it in this library. */
+/* The walk kernel (csum_kernel), or for a copy-emit number with a COPY row copy_kernel, that a launch of
+ * `variant` would run for `op` (0 data, 1 emit, 2 verify, 3 copy-emit) over a fixed-stride (`implicit` != 0)
+ * or descriptor batch, a 6LoWPAN NHC batch when `nhc`, at launch shape `shape` (0-8): out = {kernel id
+ * (1 walk, 4 NHC walk, 3 copy_kernel), the variant reported to smol_csum_tool_last_launch, G, U}.  Read from
+ * the switch and the shape mapper the launcher runs; it launches nothing.  SMOL_EINVAL: neither kernel has
+ * a launch for it in this library. */
 int smol_csum_tool_walk_launch(int variant, int op, int implicit, int nhc, int shape, int out[4]);
 
 /* The kernel (the rocprofv3 name prefix: "csum_kernel", "csum_tile_kernel", "xwalk_kernel",

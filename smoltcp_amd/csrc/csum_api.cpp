@@ -784,6 +784,11 @@ int smol_csum_tool_walk_launch(int variant, int op, int implicit, int nhc, int s
     };
     using std::integral_constant;
     bool ok = false;
+    if (op == MODE_COPY && with_copy_kernel(variant, shape, [&](auto, auto num, auto g, auto u, auto, auto) {
+            const int v[4] = {KERN_COPY, decltype(num)::value, decltype(g)::value, decltype(u)::value};
+            std::memcpy(out, v, sizeof v);
+        }))
+        return SMOL_OK;  // a COPY row: copy_kernel's launcher, whatever the batch form
     if (nhc) {
         ok = op == MODE_EMIT ? batch_form(integral_constant<int, MODE_EMIT>{}, std::true_type{})
                              : batch_form(integral_constant<int, MODE_VERIFY>{}, std::true_type{});

@@ -120,6 +120,54 @@ inline bool with_walk_kernel(int variant, int shape, Fn&& fn) {
     }
 }
 
+// copy_kernel's shape sets (csum_variants.h CopyShapes): fn(G, U, UW, UB) on the shape of SET that `shape`
+// maps to: lanes per record x body chunks per lane per round x generic round-1 slots per lane (0: enough
+// for the window plus 8 chunks) x body round-1 slots per lane.  The default, 16 x 4 x 1 x 2, takes a C2copy
+// record in two rounds: the window, its last chunk and 32 body chunks (loaded the body way), then the other 53.
+// Measured on one MI355X (tools/exp_copy.py, profiles/r02b_experiments/): 16 x 4 x 1 x 2 0.689 ms,
+// 16 x 5 x 1 x 1 0.691, 16 x 4 x 2 (body chunks in generic slots) 0.710, 16 x 3 0.743; earlier, before
+// the hi-dword loads were skipped: 16 x 4 x 2 0.738, 16 x 3 0.760, 8 x 4 x 4 0.790, 8 x 6 0.837,
+// 32 x 2 1.03, 64 x 2 1.73 (variant 16: 0.772).  Per-record work (parse, gates, window stores) is
+// issued once per wavefront for its 64 / G records, so wide groups pay it for fewer records,
+// narrow ones need more rounds.
+#define COPY_SHAPE(g, u, uw, ub)                                                        \
+    return (void)fn(std::integral_constant<int, g>{}, std::integral_constant<int, u>{}, \
+                    std::integral_constant<int, uw>{}, std::integral_constant<int, ub>{})
+template <int SET, class Fn>
+inline void with_copy_shape(int shape, Fn&& fn) {
+    if constexpr (SET == CSH_TABLE) {
+        switch (shape) {
+            case CFG_G8U6: COPY_SHAPE(8, 6, 0, 0);
+            case CFG_G8U7: COPY_SHAPE(8, 4, 4, 0);
+            case CFG_G16U3: COPY_SHAPE(16, 3, 0, 0);
+            case CFG_G16U6: COPY_SHAPE(16, 5, 1, 1);
+            case CFG_G32U3: COPY_SHAPE(16, 4, 2, 0);
+            case CFG_G32U4: COPY_SHAPE(32, 2, 1, 0);
+            case CFG_G64U2:
+            case CFG_G64U4: COPY_SHAPE(64, 2, 0, 0);
+            default: COPY_SHAPE(16, 4, 1, 2);  // CFG_G16U4
+        }
+    } else if constexpr (SET == CSH_TWO) {
+        if (shape == CFG_G16U6) COPY_SHAPE(16, 5, 1, 1);
+        COPY_SHAPE(16, 4, 1, 2);
+    } else {
+        static_assert(SET == CSH_ONE, "shape set");
+        COPY_SHAPE(16, 4, 1, 2);
+    }
+}
+#undef COPY_SHAPE
+
+// The copy_kernel a copy-emit call runs: fn(form, number reported, G, U, UW, UB), from the registry's COPY
+// rows and the shape mapper; false: the number has no COPY row built in this library.  launch_copy_kernel
+// (csum_copy.hip) launches through it and smol_csum_tool_walk_launch reads it.
+template <class Fn>
+inline bool with_copy_kernel(int variant, int shape, Fn&& fn) {
+    return with_copy_form(variant, [&](auto form, auto num) {
+        with_copy_shape<decltype(form)::SHAPES>(shape,
+                                                [&](auto g, auto u, auto uw, auto ub) { fn(form, num, g, u, uw, ub); });
+    });
+}
+
 struct KParams {
     uint8_t* buf;
     const smol_csum_desc_t* desc;  // nullptr: implicit fixed-stride batch
@@ -220,6 +268,8 @@ hipError_t launch_tile(int mode, int shape, int var, int tile_records, const KPa
 hipError_t launch_stripe(int mode, const KParams& p, hipStream_t s);
 hipError_t launch_dwalk(int mode, int variant, const KParams& p, hipStream_t s);
 hipError_t launch_xcopy(int variant, const KParams& p, hipStream_t s);
+// copy_kernel (csum_copy.hip): the class-split copy-emit kernel, the registry's COPY rows.
+hipError_t launch_copy_kernel(int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s);
 hipError_t launch_xwalk(int mode, int variant, const KParams& p, hipStream_t s);
 // Staged emit (the registry's V_STAGED variants): the staging launch writes each record's field entry to
 // p.stage, then the segment pass (csum_dwalk.hip; form 0 seg_pass4_kernel, 1 the first form, experiments

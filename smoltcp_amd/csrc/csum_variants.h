@@ -1,6 +1,6 @@
-// Reader of variants.def: the variant table and its lookups, the named forms of csum_kernel, xwalk_kernel
-// and dwalk_kernel, and the switches from (variant, mode) to a form.  Host-only (no HIP): csum_dispatch.h,
-// the launchers and the tooling entry points all read variants through this file.
+// Reader of variants.def: the variant table and its lookups, the named forms of csum_kernel, xwalk_kernel,
+// dwalk_kernel, copy_kernel and xcopy_kernel, and the switches from (variant, mode) to a form.  Host-only (no
+// HIP): csum_dispatch.h, the launchers and the tooling entry points all read variants through this file.
 #pragma once
 
 #include <stdint.h>
@@ -183,6 +183,53 @@ template <int S> struct DStaged : DG<S> { static constexpr int SEGPASS = 0; };
 using DLiteFirst = DStaged<DW_WIN_CACHED | DW_WIN_SUM | DW_LITE | DW_FIRST>;
 struct DLiteFirstPass8B : DLiteFirst { static constexpr int SEGPASS = 1; };
 
+// ---- copy_kernel's forms (csum_copy.hip) -------------------------------------------------------------
+enum CopyStore { CST_PLAIN, CST_NT, CST_WT };  // the body chunks stored with the default cache policy, non-temporal, sc1 nt
+// The launch shapes a number is built for (csum_launch.h with_copy_shape maps every CFG_* into the set).
+enum CopyShapes {
+    CSH_TABLE,  // the nine-entry table
+    CSH_TWO,    // 16 x 5 x 1 x 1 for CFG_G16U6, every other shape 16 x 4 x 1 x 2
+    CSH_ONE,    // 16 x 4 x 1 x 2 whatever the shape
+};
+struct CPlain {  // 17
+    // the first body round's loads issued right after the parse, before round 1's chunk stores, so that
+    // waiting for them does not also wait for those stores (gfx950 counts stores in vmcnt, in issue order
+    // with the loads)
+    static constexpr bool LBS = false;
+    static constexpr int BODY_STORE = CST_PLAIN;
+    static constexpr bool NT_BODY_LOADS = false;  // the body's source chunks loaded non-temporal
+    // the destination chunks of the generic (header / edge) chunks loaded non-temporal
+    static constexpr bool NT_GEN_DST = false;
+    static constexpr int SHAPES = CSH_TABLE;
+};
+// 21 (the copy-emit default): 17's default shapes with LBS.  MI355X, C2copy, interleaved rounds on one box
+// (tools/exp_copy.py, profiles/r04_experiments/copy_emit_lbs.jsonl): 16 x 4 x 1 x 2 0.678 ms against variant
+// 17's 0.692; 16 x 5 x 1 x 1 0.711; also measured and not kept: 16 x 3 x 1 x 3 0.690, 16 x 3 x 1 x 2 0.728.
+struct CLbs : CPlain { static constexpr bool LBS = true; static constexpr int SHAPES = CSH_TWO; };
+struct CLbsOne : CLbs { static constexpr int SHAPES = CSH_ONE; };  // the experiments on 21: one shape
+struct CNtStore : CLbsOne { static constexpr int BODY_STORE = CST_NT; };          // 30
+struct CNtStoreLoad : CNtStore { static constexpr bool NT_BODY_LOADS = true; };   // 22
+// 98 (round 6): whether the 28-B header reads then leave L2 as 64-B requests instead of whole 128-B lines;
+// they do not
+struct CNtGenDst : CLbsOne { static constexpr bool NT_GEN_DST = true; };
+struct CWtStore : CLbsOne { static constexpr int BODY_STORE = CST_WT; };  // 102 (round 6; cf. 30's plain nt)
+
+// ---- xcopy_kernel's forms (csum_xcopy.hip explains each constant) ----------------------------------
+struct XcPlain {  // 49
+    static constexpr bool PERSIST = false;    // a persistent grid, the next step's descriptors loaded ahead
+    static constexpr bool SRC16 = false;      // source loads rounded down to 16 B (wrong bytes, timing only)
+    static constexpr bool NOSTORE = false;    // no body stores (wrong bytes, timing only)
+    static constexpr bool CALC_DESC = false;  // the C2copy descriptors computed, not loaded (timing only)
+    static constexpr bool NT_STORES = false;  // non-temporal body stores
+    static constexpr bool REDEAL = false;     // the body chunks re-dealt through LDS, stored walk-shaped
+};
+struct XcPersist : XcPlain { static constexpr bool PERSIST = true; };      // 50
+struct XcSrc16 : XcPlain { static constexpr bool SRC16 = true; };          // 51
+struct XcNoStore : XcPlain { static constexpr bool NOSTORE = true; };      // 52
+struct XcCalcDesc : XcPlain { static constexpr bool CALC_DESC = true; };   // 53
+struct XcNtStores : XcPlain { static constexpr bool NT_STORES = true; };   // 54
+struct XcRedeal : XcPlain { static constexpr bool REDEAL = true; };        // 55
+
 #ifdef SMOL_EXP
 #define EXP_ONLY(form) form
 constexpr bool kExpBuild = true;
@@ -213,8 +260,8 @@ inline constexpr Variant kVariants[] = {
 #define WALK(n, b, fl, ft, form, scope, els, shapes, d) {n, F_WALK, V_BUILD_##b, fl, ft, SELF, 0, true, true, d},
 #define TILE(n, b, loads, d) {n, F_TILE, V_BUILD_##b, 0, SELF, SELF, loads, true, true, d},
 #define STRIPE(n, b, d) {n, F_STRIPE, V_BUILD_##b, 0, SELF, SELF, 0, true, true, d},
-#define COPY(n, b, d) {n, F_COPY, V_BUILD_##b, V_COPY_ONLY, SELF, SELF, 0, false, false, d},
-#define XCOPY(n, b, d) {n, F_XCOPY, V_BUILD_##b, V_COPY_ONLY, SELF, SELF, 0, false, false, d},
+#define COPY(n, b, form, d) {n, F_COPY, V_BUILD_##b, V_COPY_ONLY, SELF, SELF, 0, false, false, d},
+#define XCOPY(n, b, form, d) {n, F_XCOPY, V_BUILD_##b, V_COPY_ONLY, SELF, SELF, 0, false, false, d},
 #define XWALK(n, b, fl, ft, ef, vf, d) {n, F_XWALK, V_BUILD_##b, fl, ft, SELF, 0, true, true, d},
 #define DWALK(n, b, fl, ft, vt, ef, vf, d) {n, F_DWALK, V_BUILD_##b, fl, ft, vt, 0, !ef::NONE, !vf::NONE, d},
 #include "variants.def"
@@ -259,8 +306,8 @@ template <int N> struct WalkRow;  // the WALK row of number N
     };
 #define TILE(n, b, loads, d)
 #define STRIPE(n, b, d)
-#define COPY(n, b, d)
-#define XCOPY(n, b, d)
+#define COPY(n, b, form, d)
+#define XCOPY(n, b, form, d)
 #define XWALK(n, b, fl, ft, ef, vf, d)
 #define DWALK(n, b, fl, ft, vt, ef, vf, d)
 #include "variants.def"
@@ -352,11 +399,53 @@ inline bool with_dwalk_form(int variant, Fn&& fn) {
         default: return false;
     }
 }
+
+// variant -> copy_kernel's (COPY rows) / xcopy_kernel's (XCOPY rows) form: calls fn(Form{}, number), over the
+// rows built in this library; false: no such row.  The launchers instantiate the kernels through these.
+#undef COPY
+#undef XCOPY
+#define XWALK(n, b, fl, ft, ef, vf, d)
+#define DWALK(n, b, fl, ft, vt, ef, vf, d)
+#define V_ROW_P(n, form)                              \
+    case n:                                           \
+        fn(form{}, std::integral_constant<int, n>{}); \
+        return true;
+#ifdef SMOL_EXP
+#define V_ROW_X(n, form) V_ROW_P(n, form)
+#else
+#define V_ROW_X(n, form)
+#endif
+
+template <class Fn>
+inline bool with_copy_form(int variant, Fn&& fn) {
+    switch (variant) {
+#define COPY(n, b, form, d) V_ROW_##b(n, form)
+#define XCOPY(n, b, form, d)
+#include "variants.def"
+#undef COPY
+#undef XCOPY
+        default: return false;
+    }
+}
+
+template <class Fn>
+inline bool with_xcopy_form(int variant, Fn&& fn) {
+    switch (variant) {
+#define COPY(n, b, form, d)
+#define XCOPY(n, b, form, d) V_ROW_##b(n, form)
+#include "variants.def"
+#undef COPY
+#undef XCOPY
+        default: return false;
+    }
+}
+#undef XWALK
+#undef DWALK
 #undef WALK
 #undef TILE
 #undef STRIPE
-#undef COPY
-#undef XCOPY
+#undef V_ROW_P
+#undef V_ROW_X
 #undef V_FORM_P
 #undef V_FORM_X
 #undef V_BUILD_P

@@ -263,6 +263,17 @@ __device__ __forceinline__ u32x4 funnel16(const u32x4& lo, const u32x4& hi, uint
     return r;
 }
 
+// Bytes b .. b+15 of the 20 bytes (lo, hi), b in [0, 4): a chunk whose source was loaded from its first
+// byte's address rounded down to 4 (copy-emit's body chunks), shifted to the destination's alignment.
+__device__ __forceinline__ u32x4 body_shift(const u32x4& lo, uint32_t hi, uint32_t b) {
+    u32x4 m;
+    m.x = __builtin_amdgcn_alignbyte(lo.y, lo.x, b);
+    m.y = __builtin_amdgcn_alignbyte(lo.z, lo.y, b);
+    m.z = __builtin_amdgcn_alignbyte(lo.w, lo.z, b);
+    m.w = __builtin_amdgcn_alignbyte(hi, lo.w, b);
+    return m;
+}
+
 // Byte mask of dword i (bytes 4i .. 4i+3 of a chunk) for chunk-relative byte range [lo, hi).
 __device__ __forceinline__ uint32_t byte_mask(int lo, int hi, int i) { return mask_dword(0xffffffffu, lo - 4 * i, hi - 4 * i); }
 
@@ -295,6 +306,39 @@ __device__ __forceinline__ uint32_t group_sum(uint32_t v) {
     if (G >= 64) v += (uint32_t)__shfl_xor((int)v, 32, 64);
     return v;
 }
+
+// The transposed layouts' sums (csum_xwalk.hip, csum_xcopy.hip): a wavefront holds N records' partial sums
+// in every lane.
+namespace xwalk {
+
+// The value of lane ^ H (H = 32 / 16 / 8 / ..: across the wavefront, a 32-lane half, a row)
+template <int H>
+__device__ __forceinline__ uint32_t lane_xor(uint32_t v) {
+    if constexpr (H == 32) return (uint32_t)__shfl_xor((int)v, 32, 64);
+    else if constexpr (H == 16) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);
+    else return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
+}
+
+// Reduce-scatter of acc[0 .. N) over the lanes of bit H and below down to G: record j's partial sums
+// end in the lanes with (lane / G) % (N) == j.
+template <int N, int H>
+__device__ __forceinline__ uint32_t reduce_scatter(const uint32_t* acc, int wl) {
+    if constexpr (N == 1) {
+        return acc[0];
+    } else {
+        const bool up = (wl & H) != 0;
+        uint32_t a[N / 2];
+#pragma unroll
+        for (int i = 0; i < N / 2; ++i) {
+            const uint32_t keep = up ? acc[i + N / 2] : acc[i];
+            const uint32_t send = up ? acc[i] : acc[i + N / 2];
+            a[i] = keep + lane_xor<H>(send);
+        }
+        return reduce_scatter<N / 2, H / 2>(a, wl);
+    }
+}
+
+}  // namespace xwalk
 
 // The value x of lane (lane + 1) mod G of the caller's group (every lane of the group active).
 template <int G>
@@ -362,8 +406,43 @@ __device__ __forceinline__ uint32_t sum_masked_words(const u32x4& c, int lo, int
     return add_words(mask_dword(c.w, lo - 12, hi - 12), acc);
 }
 
-// The sum-and-deliver kernels' chunk helpers (csum_vcopy.hip) and, for the kernels that stream one piece
-// after the other with a whole wave (csum_fragcopy.hip, csum_fragcut.hip), the piece streamer.
+// Aligned-word sum of the chunk's bytes inside the record span [0, s1) (pos: chunk start relative to
+// the record start), as verify sums them.
+__device__ __forceinline__ uint32_t sum_chunk(const u32x4& c, int pos, int s1, uint32_t acc) {
+    if (pos >= s1 || pos + 16 <= 0) return acc;
+    if (pos < 0 || pos + 16 > s1) return sum_masked_words(c, -pos, s1 - pos, acc);
+    return add_words(c.x, add_words(c.y, add_words(c.z, add_words(c.w, acc))));
+}
+
+// Store the bytes [lo, hi) of chunk c (chunk-relative) at dst, leaving out any byte of the 2-byte fields
+// starting at chunk-relative f0 / f1 / f2 (copy-emit: finish_gates writes those).  The dword step is
+// store_dword_masked's, written out: through the call xcopy_kernel<XcPlain> compiles to 161 VGPRs instead of
+// 111, three waves per SIMD instead of four.
+__device__ __forceinline__ void store_part(gu8 dst, const u32x4& c, int lo, int hi, int f0, int f1, int f2) {
+    const bool field = (f0 > -2 && f0 < 16) || (f1 > -2 && f1 < 16) || (f2 > -2 && f2 < 16);
+    if (lo <= 0 && hi >= 16 && !field) {
+        *(GMEM u32x4*)dst = c;
+        return;
+    }
+    const uint32_t cw[4] = {c.x, c.y, c.z, c.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        uint32_t keep = byte_mask(lo, hi, i);
+        keep &= ~byte_mask(f0, f0 + 2, i);
+        keep &= ~byte_mask(f1, f1 + 2, i);
+        keep &= ~byte_mask(f2, f2 + 2, i);
+        if (keep == 0xffffffffu) {
+            *(GMEM uint32_t*)(dst + 4 * i) = cw[i];
+        } else if (keep) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (keep & (0xffu << (8 * j))) dst[4 * i + j] = (uint8_t)(cw[i] >> (8 * j));
+        }
+    }
+}
+
+// The sum-and-deliver kernels' chunk helpers (csum_vcopy.hip; sum_chunk is above) and, for the kernels that
+// stream one piece after the other with a whole wave (csum_fragcopy.hip, csum_fragcut.hip), the piece streamer.
 namespace vcopy {
 
 // The chunk the next lane of the group holds (lane G - 1: lane 0's).
@@ -375,14 +454,6 @@ __device__ __forceinline__ u32x4 next4(const u32x4& c, int lane) {
     n.z = group_next<G>(c.z, lane);
     n.w = group_next<G>(c.w, lane);
     return n;
-}
-
-// Aligned-word sum of the chunk's bytes inside the record span [0, s1) (pos: chunk start relative to
-// the record start), as verify sums them.
-__device__ __forceinline__ uint32_t sum_chunk(const u32x4& c, int pos, int s1, uint32_t acc) {
-    if (pos >= s1 || pos + 16 <= 0) return acc;
-    if (pos < 0 || pos + 16 > s1) return sum_masked_words(c, -pos, s1 - pos, acc);
-    return add_words(c.x, add_words(c.y, add_words(c.z, add_words(c.w, acc))));
 }
 
 // Store the bytes [lo, hi) of chunk c (chunk-relative) at the 16-B aligned dst: nothing is read back.
@@ -900,10 +971,7 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, T::
                 const u32x4 c = cv.s0[u];
                 u32x4 src;
                 if (A >= first && A <= last) {
-                    src.x = __builtin_amdgcn_alignbyte(c.y, c.x, b);
-                    src.y = __builtin_amdgcn_alignbyte(c.z, c.y, b);
-                    src.z = __builtin_amdgcn_alignbyte(c.w, c.z, b);
-                    src.w = __builtin_amdgcn_alignbyte(nxd, c.w, b);
+                    src = body_shift(c, nxd, b);
                 } else {  // loaded at first (shift the bytes up) or at last (down)
                     const u32x4 z = {0u, 0u, 0u, 0u};
                     src = A < first ? funnel16(z, c, (uint32_t)(16 - (first - sa))) : funnel16(c, z, (uint32_t)(sa - last));
@@ -1085,6 +1153,7 @@ __device__ __forceinline__ bool walk_step(const KParams& p, Walk& w, Regs<U, T::
             const int lo = WHOLE ? -pos : (int)w.cur.p0 - pos;
             const int hi = WHOLE ? (int)w.cur.len - pos : (int)w.cur.p1 - pos;
             if (k < w.nch && (WHOLE ? (k >= (uint32_t)WIN_CH) : (w.cur.p1 > w.cur.p0 && hi > 0 && lo < 16))) {
+                // (store_part's arithmetic, kept written out here: calling it changes all 32 of these kernels)
                 const int f0 = f0b - pos, f1 = f1b - pos, f2 = f2b - pos;
                 const bool field = (f0 > -2 && f0 < 16) || (f1 > -2 && f1 < 16) || (f2 > -2 && f2 < 16);
                 const gu8 dst = cbase + 16u * k;

@@ -1,5 +1,6 @@
-// Dispatches a batched call to the walk kernel instantiation for its mode and batch form (and, in the
-// experiments build, instantiates the walk kernel's MODE_COPY forms: launch_walk<MODE_COPY, ...>).
+// Dispatches a batched call to the walk kernel instantiation for its mode and batch form, copy-emit to
+// copy_kernel's launcher (csum_copy.hip) where the number has a COPY row (and, in the experiments build,
+// instantiates the walk kernel's MODE_COPY forms: launch_walk<MODE_COPY, ...>).
 #include "csum_walk.h"
 
 namespace smolcsum {
@@ -15,32 +16,6 @@ extern template hipError_t launch_walk_nhc<MODE_EMIT, true>(int, int, const KPar
 extern template hipError_t launch_walk_nhc<MODE_EMIT, false>(int, int, const KParams&, uint32_t, hipStream_t);
 extern template hipError_t launch_walk_nhc<MODE_VERIFY, true>(int, int, const KParams&, uint32_t, hipStream_t);
 extern template hipError_t launch_walk_nhc<MODE_VERIFY, false>(int, int, const KParams&, uint32_t, hipStream_t);
-
-// variant 17: the class-split copy-emit kernel (csum_copy.hip)
-hipError_t launch_copy_v17(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s);
-// variant 21: variant 17 with the first body round's loads ahead of round 1's stores (csum_copy.hip)
-hipError_t launch_copy_v21(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s);
-#ifdef SMOL_EXP
-// variants 30 / 22: 21 with non-temporal body stores / and source loads (csum_copy.hip)
-hipError_t launch_copy_nt(int var, const KParams& p, uint32_t max_blocks, hipStream_t s);
-#endif
-
-// 17 / 21 (copy_kernel) are the product's; the walk kernel's MODE_COPY forms (the registry's V_WALK_COPY
-// rows 1, 8, 11, 16: the round-1 / 2 designs) are in the experiments build only.
-template <bool IMPLICIT>
-hipError_t launch_copy(int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s) {
-    switch (var) {
-        case 17: return launch_copy_v17(shape, p, max_blocks, s);
-        case 21: return launch_copy_v21(shape, p, max_blocks, s);
-#ifdef SMOL_EXP
-        case 30:
-        case 98:
-        case 102:
-        case 22: return launch_copy_nt(var, p, max_blocks, s);
-#endif
-        default: return launch_walk<MODE_COPY, IMPLICIT>(shape, var, p, max_blocks, s);
-    }
-}
 
 hipError_t launch_csum(int mode, int shape, int var, const KParams& p, uint32_t max_blocks, hipStream_t s) {
     const bool implicit = p.desc == nullptr;
@@ -60,8 +35,15 @@ hipError_t launch_csum(int mode, int shape, int var, const KParams& p, uint32_t 
         case MODE_EMIT:
             return implicit ? launch_walk<MODE_EMIT, true>(shape, var, p, max_blocks, s)
                             : launch_walk<MODE_EMIT, false>(shape, var, p, max_blocks, s);
-        case MODE_COPY:
-            return implicit ? launch_copy<true>(shape, var, p, max_blocks, s) : launch_copy<false>(shape, var, p, max_blocks, s);
+        case MODE_COPY: {
+            // a COPY row's number (17 / 21 are the product's) runs copy_kernel; any other the walk kernel's
+            // MODE_COPY form of it (the registry's V_WALK_COPY rows 1, 8, 11, 16: the round-1 / 2 designs,
+            // in the experiments build only)
+            const Variant* row = find_variant(var);
+            if (row && row->family == F_COPY) return launch_copy_kernel(shape, var, p, max_blocks, s);
+            return implicit ? launch_walk<MODE_COPY, true>(shape, var, p, max_blocks, s)
+                            : launch_walk<MODE_COPY, false>(shape, var, p, max_blocks, s);
+        }
         default:
             return implicit ? launch_walk<MODE_VERIFY, true>(shape, var, p, max_blocks, s)
                             : launch_walk<MODE_VERIFY, false>(shape, var, p, max_blocks, s);

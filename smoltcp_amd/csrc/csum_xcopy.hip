@@ -20,7 +20,7 @@
 // Aligned 16-B source chunks are loaded only when they overlap the payload, and a dwordx4 from a
 // 4-byte-aligned address only when all of its chunk's 16 bytes are payload, so no load touches a
 // page that holds none of the source range.
-#include "csum_walk.h"
+#include "csum_copyemit.h"
 
 namespace smolcsum {
 
@@ -33,101 +33,48 @@ constexpr int G = 8;        // lanes per record (parse, gates)
 constexpr int NS = 2;       // body load instructions per record (64 chunks each)
 constexpr int WAVES = 4;
 constexpr int GPB = WAVES * R;
-constexpr int WIN = 128;    // the header window on the 16-B grid
-constexpr int WIN_CH = WIN / 16;
-constexpr int NOF = -(1 << 20);
+using namespace copyemit;  // WIN, RecGeom, gen_load / gen_merge, far_fields, ByteReader
 
-// Store the bytes [lo, hi) of chunk c (chunk-relative), leaving out the 2-byte fields at f0 / f1 / f2.
-__device__ __forceinline__ void store_part(gu8 dst, const u32x4& c, int lo, int hi, int f0, int f1, int f2) {
-    const bool field = (f0 > -2 && f0 < 16) || (f1 > -2 && f1 < 16) || (f2 > -2 && f2 < 16);
-    if (lo <= 0 && hi >= 16 && !field) {
-        *(GMEM u32x4*)dst = c;
-        return;
-    }
-    const uint32_t cw[4] = {c.x, c.y, c.z, c.w};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        uint32_t keep = byte_mask(lo, hi, i);
-        keep &= ~byte_mask(f0, f0 + 2, i);
-        keep &= ~byte_mask(f1, f1 + 2, i);
-        keep &= ~byte_mask(f2, f2 + 2, i);
-        if (keep == 0xffffffffu) {
-            *(GMEM uint32_t*)(dst + 4 * i) = cw[i];
-        } else if (keep) {
-#pragma unroll
-            for (int b = 0; b < 4; ++b)
-                if (keep & (0xffu << (8 * b))) dst[4 * i + b] = (uint8_t)(cw[i] >> (8 * b));
-        }
-    }
-}
-
-// Aligned-word sum of the chunk's bytes inside [0, s1) (pos: chunk start relative to the record).
-__device__ __forceinline__ uint32_t sum_chunk(const u32x4& c, int pos, int s1, uint32_t acc) {
-    if (pos >= s1 || pos + 16 <= 0) return acc;
-    if (pos < 0 || pos + 16 > s1) return sum_masked_words(c, -pos, s1 - pos, acc);
-    return add_words(c.x, add_words(c.y, add_words(c.z, add_words(c.w, acc))));
-}
-
-// One record's copy geometry (wave-uniform values for the fast layout).
-struct Rec {
-    uint64_t a0, base, sb;  // record start, its 16-B grid origin, source address of record offset 0
-    uint32_t head, nch, p0, p1;
-    bool bad;
+// What the parse leaves a group: the record's geometry, the end of its summed span (0: no L4 sum) and the
+// fields past the window, which stay out of the chunk stores (finish_gates writes them).
+struct Parsed {
+    Geom g;
+    int s1;
+    FarFields ff;
 };
-
-// Chunk k of a record built the generic way: the destination chunk (unless all payload) and the two
-// aligned source chunks under its payload bytes (clamped into the source range's aligned chunks).
-struct Gen {
-    u32x4 d, c0, c1;
-};
-__device__ __forceinline__ Gen gen_load(const Rec& q, uint32_t k, bool in, uint64_t dummy) {
-    const int pos = (int)(16u * k) - (int)q.head;
-    const int lo = (int)q.p0 - pos, hi = (int)q.p1 - pos;
-    const bool pay = q.p1 > q.p0;
-    const bool full = lo <= 0 && hi >= 16;
-    const bool any = pay && lo < 16 && hi > 0;
-    const uint64_t sk = q.sb - q.head;
-    const uint64_t first = (q.sb + q.p0) & ~15ull, last = (q.sb + q.p1 - 1) & ~15ull;
-    const uint64_t sA = (sk + 16ull * k) & ~15ull;
-    const uint64_t a0 = sA < first ? first : sA > last ? last : sA;
-    const uint64_t a1 = sA + 16 < first ? first : sA + 16 > last ? last : sA + 16;
-    Gen g;
-    g.d = ld16<false>((gcv4)(in && !(pay && full) ? q.base + 16ull * k : dummy));
-    g.c0 = ld16<false>((gcv4)(in && any ? a0 : dummy));
-    g.c1 = ld16<false>((gcv4)(in && any && (sk & 15u) ? a1 : dummy));
-    return g;
-}
-__device__ __forceinline__ u32x4 gen_merge(const Rec& q, uint32_t k, const Gen& g) {
-    const int pos = (int)(16u * k) - (int)q.head;
-    const int lo = (int)q.p0 - pos, hi = (int)q.p1 - pos;
-    if (!(q.p1 > q.p0 && lo < 16 && hi > 0)) return g.d;
-    const u32x4 s = funnel16(g.c0, g.c1, (uint32_t)((q.sb - q.head) & 15u));
-    if (lo <= 0 && hi >= 16) return s;
-    u32x4 m;
-    const uint32_t m0 = byte_mask(lo, hi, 0), m1 = byte_mask(lo, hi, 1);
-    const uint32_t m2 = byte_mask(lo, hi, 2), m3 = byte_mask(lo, hi, 3);
-    m.x = (s.x & m0) | (g.d.x & ~m0);
-    m.y = (s.y & m1) | (g.d.y & ~m1);
-    m.z = (s.z & m2) | (g.d.z & ~m2);
-    m.w = (s.w & m3) | (g.d.w & ~m3);
-    return m;
+// The group's window chunk wm of lane `lane` into LDS (has: the chunk exists), then the parse (mine: the
+// group has a record).
+__device__ __forceinline__ Parsed parse_window(u32x4* wn, int lane, const u32x4& wm, bool has, bool mine,
+                                               const ByteReader& rd, uint32_t len, uint32_t kind) {
+    if (has) wn[lane] = wm;
+    wave_lds_sync();
+    Parsed ps;
+    ps.g = Geom{};
+    if (mine) ps.g = parse_geometry<false>(rd, len, kind, true);
+    const bool l4 = ps.g.proto != P_NONE && !(ps.g.st & SMOL_ST_MALFORMED);
+    ps.s1 = mine && l4 ? (int)ps.g.span_end : 0;
+    if (mine) ps.ff = far_fields(ps.g, rd.q.head, WIN);
+    return ps;
 }
 
 }  // namespace xcopy
 
+// F: the form, one of csum_variants.h's named structs (XcPlain and what differs from it); variants.def says
+// which number runs which.  Its constants:
 // PERSIST (variant 50): a grid of the resident workgroups whose wavefronts step over the batch 8 records
 // at a time, loading the next step's copy descriptors ahead, so that a step waits for one round
 // trip (its loads) instead of two (the descriptors, then the loads that need them).
-// EXPT (variants 51-53, timing only, wrong bytes): 1 source loads rounded down to 16 B instead of
-// 4; 2 no body stores; 4 the C2copy descriptors computed, not loaded (src_offset 1472 r, dst 28).
-// 8 (variant 54, exact): non-temporal body stores.  16 (variant 55, exact): the body chunks re-dealt
-// through LDS and stored walk-shaped, each store instruction covering 128 B of each of the 8 records.
-template <bool PERSIST, int EXPT = 0>
+// SRC16, NOSTORE, CALC_DESC (variants 51-53, timing only, wrong bytes): source loads rounded down to 16 B
+// instead of 4; no body stores; the C2copy descriptors computed, not loaded (src_offset 1472 r, dst 28).
+// NT_STORES (variant 54, exact): non-temporal body stores.  REDEAL (variant 55, exact): the body chunks
+// re-dealt through LDS and stored walk-shaped, each store instruction covering 128 B of each of the 8 records.
+template <class F>
 __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
     using namespace xcopy;
+    constexpr bool PERSIST = F::PERSIST, REDEAL = F::REDEAL;
     __shared__ u32x4 win[GPB][WIN_CH];
     __shared__ uint32_t spanbuf[GPB];
-    __shared__ u32x4 stg[(EXPT & 16) ? WAVES : 1][(EXPT & 16) ? R : 1][64];  // EXPT 16: one half-step's body chunks
+    __shared__ u32x4 stg[REDEAL ? WAVES : 1][REDEAL ? R : 1][64];  // REDEAL: one half-step's body chunks
     const int wl = (int)(threadIdx.x & 63);
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int lane = wl & (G - 1);
@@ -152,28 +99,24 @@ __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
     const uint32_t cnt = (uint32_t)(p.n - rw0 < (uint64_t)R ? p.n - rw0 : (uint64_t)R);
     const bool mine = (uint32_t)gw < cnt;
     const uint64_t r = rw0 + (uint64_t)gw;
-    Rec q;  // the group's own record (per-lane values, equal within the group)
-    q.a0 = (uint64_t)p.buf + r * p.stride;
-    q.base = q.a0 & ~15ull;
-    q.head = (uint32_t)(q.a0 - q.base);
-    q.nch = (uint32_t)(((q.a0 + len + 15) >> 4) - (q.base >> 4));
     // this group's descriptor from lane gw
-    {
-        const uint32_t cx = (uint32_t)__shfl((int)dsc.x, gw, 64), cy = (uint32_t)__shfl((int)dsc.y, gw, 64);
-        const uint32_t cz = (uint32_t)__shfl((int)dsc.z, gw, 64), cw = (uint32_t)__shfl((int)dsc.w, gw, 64);
-        q.bad = (uint64_t)cz + cw > len;
-        q.p0 = q.bad ? 0u : cz;
-        q.p1 = q.bad ? 0u : cz + cw;
-        q.sb = q.bad ? 0ull : (uint64_t)p.src + ((uint64_t)cx | ((uint64_t)cy << 32)) - cz;
-        if (EXPT & 4) {
-            q.bad = false;
-            q.p0 = 28;
-            q.p1 = len;
-            q.sb = (uint64_t)p.src + 1472ull * r - 28;
-        }
-    }
-    const bool fast_rec = !mine || (!q.bad && q.p1 > q.p0 && q.p1 == len && q.head + q.p0 <= (uint32_t)WIN);
+    const uint32_t cx = (uint32_t)__shfl((int)dsc.x, gw, 64), cy = (uint32_t)__shfl((int)dsc.y, gw, 64);
+    const uint32_t cz = (uint32_t)__shfl((int)dsc.z, gw, 64), cw = (uint32_t)__shfl((int)dsc.w, gw, 64);
+    const bool bad = !F::CALC_DESC && (uint64_t)cz + cw > len;  // the copy range does not fit
+    // the payload [p0, p1) of the record, from sb + p0 (CALC_DESC: src_offset 1472 r, dst 28)
+    const uint32_t p0 = F::CALC_DESC ? 28u : bad ? 0u : cz;
+    const uint32_t p1 = F::CALC_DESC ? len : bad ? 0u : cz + cw;
+    const uint64_t sb = F::CALC_DESC ? (uint64_t)p.src + 1472ull * r - 28
+                        : bad        ? 0ull
+                                     : (uint64_t)p.src + ((uint64_t)cx | ((uint64_t)cy << 32)) - cz;
+    const uint64_t a0 = (uint64_t)p.buf + r * p.stride;
+    // the group's own record (per-lane values, equal within the group)
+    const RecGeom q(a0, (uint32_t)(((a0 + len + 15) >> 4) - (a0 >> 4)), sb, p0, p1);
+    const bool fast_rec = !mine || (!bad && q.p1 > q.p0 && q.p1 == len && q.head + q.p0 <= (uint32_t)WIN);
     const bool fast = __all(fast_rec);
+    u32x4* wn = &win[gib][0];
+    const uint8_t* winb = reinterpret_cast<const uint8_t*>(wn);
+    const ByteReader rd{winb, q};
 
     if (fast) {
         // ---- window sources (group j, lane i: chunk i) and the edge chunk's (lane 0) ----
@@ -193,12 +136,12 @@ __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
             uint64_t so = (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)dsc.x, j) |
                           ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)dsc.y, j) << 32);
             uint32_t dz = (uint32_t)__builtin_amdgcn_readlane((int)dsc.z, j);
-            if (EXPT & 4) {
+            if (F::CALC_DESC) {
                 so = 1472ull * (rw0 + (uint64_t)j);
                 dz = 28;
             }
             const uint64_t sk = (uint64_t)p.src + so - dz - h;
-            const uint64_t skA = (EXPT & 1) ? (sk & ~15ull) : (sk & ~3ull);
+            const uint64_t skA = F::SRC16 ? (sk & ~15ull) : (sk & ~3ull);
             bsh[j] = (uint32_t)(sk & 3u);
             hd[j] = h;
             nb[j] = (uint32_t)j < cnt ? nc - 1 : 0u;  // body chunks are [8, nb)
@@ -214,39 +157,16 @@ __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
         }
         // ---- the window into LDS, the parse ----
         const u32x4 wm = gen_merge(q, (uint32_t)lane, gwin);
-        if (mine) win[gib][lane] = wm;
-        wave_lds_sync();
-        const uint8_t* winb = reinterpret_cast<const uint8_t*>(&win[gib][0]);
-        auto rd = [&](uint32_t o) -> uint32_t {
-            const uint32_t x = q.head + o;
-            if (x < (uint32_t)WIN) return (uint32_t)winb[x];
-            if (o >= q.p0 && o < q.p1) return ld_byte_sync(q.sb + o);
-            return ld_byte_sync(q.a0 + o);
-        };
-        Geom g = Geom{};
-        if (mine) g = parse_geometry<false>(rd, len, p.kind, true);
-        const bool l4 = g.proto != P_NONE && !(g.st & SMOL_ST_MALFORMED);
-        const int s1 = mine && l4 ? (int)g.span_end : 0;
-        // fields past the window stay out of the chunk stores (finish_gates writes them)
-        int f0b = NOF, f1b = NOF, f2b = NOF;
-        {
-            const uint32_t fip = g.fam == 4 ? g.ip_off + 10 : NO_FIELD;
-            const uint32_t fl4 = l4 ? g.l4_off + g.fo : NO_FIELD;
-            const uint32_t fin = g.in_off ? g.in_off + 10 : NO_FIELD;
-            auto past = [&](uint32_t f) { return f != NO_FIELD && q.head + f + 2 > (uint32_t)WIN; };
-            if (mine && (past(fip) || past(fl4) || past(fin))) {
-                f0b = fip != NO_FIELD ? (int)fip : NOF;
-                f1b = fl4 != NO_FIELD ? (int)fl4 : NOF;
-                f2b = fin != NO_FIELD ? (int)fin : NOF;
-            }
-        }
+        const Parsed ps = parse_window(wn, lane, wm, mine, mine, rd, len, p.kind);
+        const Geom& g = ps.g;
+        const int s1 = ps.s1, f0b = ps.ff.f0, f1b = ps.ff.f1, f2b = ps.ff.f2;
         if (lane == 0) spanbuf[gib] = (uint32_t)s1;
         // far fields of record j, for the body stores (rare: behind a long Hop-by-Hop header)
-        const bool any_far = __any(f0b != NOF || f1b != NOF || f2b != NOF);
+        const bool any_far = __any(ps.ff.any());
         wave_lds_sync();
         // ---- body: shift, sum, store ----
         uint32_t acc[R];
-        if constexpr ((EXPT & 16) != 0) {
+        if constexpr (REDEAL) {
 #pragma unroll
             for (int j = 0; j < R; ++j) acc[j] = 0;
 #pragma unroll
@@ -256,13 +176,7 @@ __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
                     const int sj = (int)spanbuf[wv * R + j], hj = (int)hd[j];
                     const uint32_t k = (uint32_t)(64 * s + wl);
                     const bool in = k >= (uint32_t)WIN_CH && k < nb[j];
-                    const u32x4 lo = v[s][j];
-                    const uint32_t b = bsh[j];
-                    u32x4 m;
-                    m.x = __builtin_amdgcn_alignbyte(lo.y, lo.x, b);
-                    m.y = __builtin_amdgcn_alignbyte(lo.z, lo.y, b);
-                    m.z = __builtin_amdgcn_alignbyte(lo.w, lo.z, b);
-                    m.w = __builtin_amdgcn_alignbyte(vh[s][j], lo.w, b);
+                    const u32x4 m = body_shift(v[s][j], vh[s][j], bsh[j]);
                     if (in) acc[j] = sum_chunk(m, 16 * (int)k - hj, sj, acc[j]);
                     stg[wv][j][wl] = m;
                 }
@@ -297,19 +211,13 @@ __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
             for (int s = 0; s < NS; ++s) {
                 const uint32_t k = (uint32_t)(64 * s + wl);
                 const bool in = k >= (uint32_t)WIN_CH && k < nb[j];
-                const u32x4 lo = v[s][j];
-                const uint32_t b = bsh[j];
-                u32x4 m;
-                m.x = __builtin_amdgcn_alignbyte(lo.y, lo.x, b);
-                m.y = __builtin_amdgcn_alignbyte(lo.z, lo.y, b);
-                m.z = __builtin_amdgcn_alignbyte(lo.w, lo.z, b);
-                m.w = __builtin_amdgcn_alignbyte(vh[s][j], lo.w, b);
+                const u32x4 m = body_shift(v[s][j], vh[s][j], bsh[j]);
                 const int pos = 16 * (int)k - hj;
                 if (in) {
                     acc[j] = sum_chunk(m, pos, sj, acc[j]);
                     const gu8 dst = (gu8)base + 16u * k;
-                    if (EXPT & 2) asm volatile("" ::"v"(m.x), "v"(m.y), "v"(m.z), "v"(m.w));
-                    else if ((EXPT & 8) && !any_far) __builtin_nontemporal_store(m, (GMEM u32x4*)dst);
+                    if (F::NOSTORE) asm volatile("" ::"v"(m.x), "v"(m.y), "v"(m.z), "v"(m.w));
+                    else if (F::NT_STORES && !any_far) __builtin_nontemporal_store(m, (GMEM u32x4*)dst);
                     else if (!any_far) *(GMEM u32x4*)dst = m;
                     else store_part(dst, m, 0, 16, F0 - pos, F1 - pos, F2 - pos);
                 }
@@ -328,60 +236,26 @@ __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
                            f2b - pose);
             }
         }
-        // (reduce_scatter of csum_xwalk.hip, inlined: 32, 16, 8)
-        uint32_t a4[4], a2[2];
-        const bool up32 = (wl & 32) != 0, up16 = (wl & 16) != 0, up8 = (wl & 8) != 0;
-#pragma unroll
-        for (int i = 0; i < 4; ++i)
-            a4[i] = (up32 ? acc[i + 4] : acc[i]) + (uint32_t)__shfl_xor((int)(up32 ? acc[i] : acc[i + 4]), 32, 64);
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-            a2[i] = (up16 ? a4[i + 2] : a4[i]) +
-                    (uint32_t)__builtin_amdgcn_ds_swizzle((int)(up16 ? a4[i] : a4[i + 2]), 0x401F);
-        const uint32_t a1 = (up8 ? a2[1] : a2[0]) +
-                            (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(up8 ? a2[0] : a2[1]), 0x128, 0xF, 0xF, false);
+        const uint32_t a1 = xwalk::reduce_scatter<R, 32>(acc, wl);
         // ---- finish: gates, fields into the window (or past it), then the window chunks ----
         if (mine) {
-            finish_gates<G, MODE_COPY, false, decltype(rd), WIN>(p, g, a1 + own, rd, winb, q.head, q.a0, r, lane,
-                                                                  reinterpret_cast<uint8_t*>(&win[gib][0]));
+            finish_gates<G, MODE_COPY, false, ByteReader, WIN>(p, g, a1 + own, rd, winb, q.head, q.a0, r, lane,
+                                                                reinterpret_cast<uint8_t*>(wn));
         }
         wave_lds_sync();
         if (mine) {
             const int posw = 16 * lane - (int)q.head;
             store_part((gu8)q.base + 16u * (uint32_t)lane, win[gib][lane], -posw, (int)len - posw, NOF, NOF, NOF);
         }
-    } else if (mine && q.bad) {  // the copy range does not fit: record left untouched
+    } else if (mine && bad) {  // the copy range does not fit: record left untouched
         if (lane == 0 && p.status) ((gu8)p.status)[r] = (uint8_t)SMOL_ST_MALFORMED;
     } else if (mine) {
     // ---- generic path: group j builds every chunk of record j the window's way ----
-    {
-        const Gen gw0 = gen_load(q, (uint32_t)lane, lane < (int)q.nch, dummy);
-        const u32x4 wm = gen_merge(q, (uint32_t)lane, gw0);
-        if ((uint32_t)lane < q.nch) win[gib][lane] = wm;
-    }
-    wave_lds_sync();
-    const uint8_t* winb = reinterpret_cast<const uint8_t*>(&win[gib][0]);
-    auto rd = [&](uint32_t o) -> uint32_t {
-        const uint32_t x = q.head + o;
-        if (x < (uint32_t)WIN) return (uint32_t)winb[x];
-        if (o >= q.p0 && o < q.p1) return ld_byte_sync(q.sb + o);
-        return ld_byte_sync(q.a0 + o);
-    };
-    const Geom g = parse_geometry<false>(rd, len, p.kind, true);
-    const bool l4 = g.proto != P_NONE && !(g.st & SMOL_ST_MALFORMED);
-    const int s1 = l4 ? (int)g.span_end : 0;
-    int f0b = NOF, f1b = NOF, f2b = NOF;
-    {
-        const uint32_t fip = g.fam == 4 ? g.ip_off + 10 : NO_FIELD;
-        const uint32_t fl4 = l4 ? g.l4_off + g.fo : NO_FIELD;
-        const uint32_t fin = g.in_off ? g.in_off + 10 : NO_FIELD;
-        auto past = [&](uint32_t f) { return f != NO_FIELD && q.head + f + 2 > (uint32_t)WIN; };
-        if (past(fip) || past(fl4) || past(fin)) {
-            f0b = fip != NO_FIELD ? (int)fip : NOF;
-            f1b = fl4 != NO_FIELD ? (int)fl4 : NOF;
-            f2b = fin != NO_FIELD ? (int)fin : NOF;
-        }
-    }
+    const Gen gwin = gen_load(q, (uint32_t)lane, lane < (int)q.nch, dummy);
+    const Parsed ps =
+        parse_window(wn, lane, gen_merge(q, (uint32_t)lane, gwin), (uint32_t)lane < q.nch, true, rd, len, p.kind);
+    const Geom& g = ps.g;
+    const int s1 = ps.s1, f0b = ps.ff.f0, f1b = ps.ff.f1, f2b = ps.ff.f2;
     uint32_t acc = 0;
     if ((uint32_t)lane < q.nch) acc = sum_chunk(win[gib][lane], 16 * lane - (int)q.head, s1, 0u);
     for (uint32_t k0 = WIN_CH; k0 < q.nch; k0 += G) {
@@ -395,8 +269,8 @@ __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
             store_part((gu8)q.base + 16u * k, m, -pos, (int)len - pos, f0b - pos, f1b - pos, f2b - pos);
         }
     }
-    finish_gates<G, MODE_COPY, false, decltype(rd), WIN>(p, g, acc, rd, winb, q.head, q.a0, r, lane,
-                                                          reinterpret_cast<uint8_t*>(&win[gib][0]));
+    finish_gates<G, MODE_COPY, false, ByteReader, WIN>(p, g, acc, rd, winb, q.head, q.a0, r, lane,
+                                                        reinterpret_cast<uint8_t*>(wn));
     wave_lds_sync();
     if ((uint32_t)lane < q.nch) {
         const int posw = 16 * lane - (int)q.head;
@@ -410,38 +284,37 @@ __global__ __launch_bounds__(256) void xcopy_kernel(KParams p) {
 
 #endif  // SMOL_EXP
 
+// A number without an XCOPY row built in this library is an error (the dispatch passes none).
 hipError_t launch_xcopy(int variant, const KParams& p, hipStream_t s) {
+    hipError_t e = hipErrorInvalidValue;
 #ifdef SMOL_EXP
-    const uint64_t per = (uint64_t)xcopy::GPB;
-    note_launch(KERN_COPY, (uint32_t)variant, 8, 2);
-    if (variant == 50) {  // persistent: the workgroups resident at once
-        const uint32_t cap = resident_blocks((const void*)xcopy_kernel<true>, p.num_cu ? p.num_cu : 256u,
-                                             (uint32_t)kMaxGridBlocks);
-        const uint32_t b = grid_blocks((p.n + per - 1) / per, cap);
-        hipLaunchKernelGGL((xcopy_kernel<true>), dim3(b), dim3(256), 0, s, p);
-        return hipGetLastError();
-    }
-    const uint64_t span = kMaxGridBlocks * per;
-    for (uint64_t i0 = 0; i0 < p.n; i0 += span) {
-        KParams q = p;
-        q.n = p.n - i0 < span ? p.n - i0 : span;
-        q.buf = p.buf + i0 * p.stride;
-        q.copy = p.copy + i0;
-        if (p.status) q.status = p.status + i0;
-        const uint32_t b = grid_blocks((q.n + per - 1) / per, kMaxGridBlocks);
-        if (variant == 51) hipLaunchKernelGGL((xcopy_kernel<false, 1>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 52) hipLaunchKernelGGL((xcopy_kernel<false, 2>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 53) hipLaunchKernelGGL((xcopy_kernel<false, 4>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 54) hipLaunchKernelGGL((xcopy_kernel<false, 8>), dim3(b), dim3(256), 0, s, q);
-        else if (variant == 55) hipLaunchKernelGGL((xcopy_kernel<false, 16>), dim3(b), dim3(256), 0, s, q);
-        else hipLaunchKernelGGL((xcopy_kernel<false>), dim3(b), dim3(256), 0, s, q);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
-#else
-    return hipErrorInvalidValue;
+    with_xcopy_form(variant, [&](auto form, auto num) {
+        using F = decltype(form);
+        const uint64_t per = (uint64_t)xcopy::GPB;
+        note_launch(KERN_COPY, decltype(num)::value, 8, 2);
+        if constexpr (F::PERSIST) {  // the workgroups resident at once
+            const uint32_t cap = resident_blocks((const void*)xcopy_kernel<F>, p.num_cu ? p.num_cu : 256u,
+                                                 (uint32_t)kMaxGridBlocks);
+            const uint32_t b = grid_blocks((p.n + per - 1) / per, cap);
+            hipLaunchKernelGGL((xcopy_kernel<F>), dim3(b), dim3(256), 0, s, p);
+            e = hipGetLastError();
+        } else {
+            const uint64_t span = kMaxGridBlocks * per;
+            e = hipSuccess;
+            for (uint64_t i0 = 0; i0 < p.n && e == hipSuccess; i0 += span) {
+                KParams q = p;
+                q.n = p.n - i0 < span ? p.n - i0 : span;
+                q.buf = p.buf + i0 * p.stride;
+                q.copy = p.copy + i0;
+                if (p.status) q.status = p.status + i0;
+                const uint32_t b = grid_blocks((q.n + per - 1) / per, kMaxGridBlocks);
+                hipLaunchKernelGGL((xcopy_kernel<F>), dim3(b), dim3(256), 0, s, q);
+                e = hipGetLastError();
+            }
+        }
+    });
 #endif
+    return e;
 }
 
 }  // namespace smolcsum

@@ -39,32 +39,7 @@ namespace xwalk {
 constexpr int WIN_CH = 16;  // the LDS window: 256 B from the record's 128-B line
 constexpr int WAVES = 4;    // wavefronts per workgroup
 
-// The value of lane ^ H (H = 32 / 16 / 8 / ..: across the wavefront, a 32-lane half, a row)
-template <int H>
-__device__ __forceinline__ uint32_t lane_xor(uint32_t v) {
-    if constexpr (H == 32) return (uint32_t)__shfl_xor((int)v, 32, 64);
-    else if constexpr (H == 16) return (uint32_t)__builtin_amdgcn_ds_swizzle((int)v, 0x401F);
-    else return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, 0x128, 0xF, 0xF, false);  // row_ror:8
-}
-
-// Reduce-scatter of acc[0 .. N) over the lanes of bit H and below down to G: record j's partial sums
-// end in the lanes with (lane / G) % (N) == j.
-template <int N, int H>
-__device__ __forceinline__ uint32_t reduce_scatter(const uint32_t* acc, int wl) {
-    if constexpr (N == 1) {
-        return acc[0];
-    } else {
-        const bool up = (wl & H) != 0;
-        uint32_t a[N / 2];
-#pragma unroll
-        for (int i = 0; i < N / 2; ++i) {
-            const uint32_t keep = up ? acc[i + N / 2] : acc[i];
-            const uint32_t send = up ? acc[i] : acc[i + N / 2];
-            a[i] = keep + lane_xor<H>(send);
-        }
-        return reduce_scatter<N / 2, H / 2>(a, wl);
-    }
-}
+// lane_xor, reduce_scatter: csum_walk.h (shared with csum_xcopy.hip)
 
 }  // namespace xwalk
 

@@ -247,8 +247,9 @@ def test_kernel_forms_match_recorded_table():
 
 
 def test_walk_launches_match_recorded_table():
-    """The walk kernel's launcher (smol_csum_tool_walk_launch: the registry switch and the shape mapper
-    that launch_walk / launch_walk_nhc run) launches what the commit before the named walk forms launched.
+    """The walk kernel's and copy_kernel's launchers (smol_csum_tool_walk_launch: the registry switches and the
+    shape mappers that launch_walk / launch_walk_nhc / launch_copy_kernel run) launch what the commit before
+    the named walk forms launched.
     tests/data/walk_launch_parent.jsonl was recorded from that commit, never from the code under test: a
     program linked against each of its two libraries called smolcsum::launch_csum for every variant
     0-127, data / emit / verify / copy-emit, fixed-stride and descriptor batches, NHC on and off and all
@@ -256,8 +257,8 @@ def test_walk_launches_match_recorded_table():
     (note_launch runs before the launch), with a sentinel launch of another kernel family between probes
     to tell the calls that launch nothing apart.  One line per (library, variant, op, batch form, nhc)
     that launched anything, with the nine packed last_launch values; a missing line is an error for all
-    nine.  Lines whose kernel id is not the walk's (copy_kernel's 17 / 21 / 22 / 30 / 98 / 102) are not
-    the walk launcher's to answer."""
+    nine.  Every line is served: the walk's, the NHC walk's and copy_kernel's (17 / 21 / 22 / 30 / 98 / 102,
+    kernel id 3)."""
     import json
 
     want = {}
@@ -280,7 +281,8 @@ def test_walk_launches_match_recorded_table():
                             rc = L.smol_csum_tool_walk_launch(v, op, implicit, nhc, shape, out)
                             exp = rec[shape]
                             where = (name, v, op, implicit, nhc, shape)
-                            if exp != "error" and exp >> 24 in (1, 4):  # KERN_WALK, KERN_WALK_NHC
+                            if exp != "error":
+                                assert exp >> 24 in (1, 3, 4)  # KERN_WALK, KERN_COPY, KERN_WALK_NHC
                                 assert rc == 0, where
                                 assert out[0] << 24 | out[1] << 16 | out[2] << 8 | out[3] == exp, (where, list(out), exp)
                                 served += 1
@@ -288,4 +290,4 @@ def test_walk_launches_match_recorded_table():
                                 assert rc == _lib.SMOL_EINVAL, (where, list(out))
         assert L.smol_csum_tool_walk_launch(5, 4, 1, 0, 0, out) == _lib.SMOL_EINVAL
         assert L.smol_csum_tool_walk_launch(5, 1, 1, 0, 9, out) == _lib.SMOL_EINVAL
-    assert served > 9 * 1000
+    assert served == 9 * 1235

@@ -120,7 +120,7 @@ def _run(eng, recs, copies_spec, caps=(0, 0, 0, 0, 0), shape=-1, fixed_stride=No
     if n:  # the forced variant ran its own kernel (default: copy_kernel variant 21)
         want = ("csum_kernel", variant) if variant in (1, 8, 11, 16) else \
             ("copy_kernel", variant if variant in (17, 22, 30, 98, 102) else 21)
-        if variant in (49, 50, 55) and fixed_stride and 1024 <= (fixed_len or fixed_stride) <= 1921:
+        if variant in (49, 50, 54, 55) and fixed_stride and 1024 <= (fixed_len or fixed_stride) <= 1921:
             want = ("copy_kernel", variant)  # the transposed layout (csum_xcopy.hip)
         assert (launched["kernel"], launched["variant"]) == want, (variant, launched)
     diff = np.nonzero(got != ref)[0]
@@ -193,10 +193,11 @@ def test_copy_emit_fixed_stride_mixed(eng, stride, length):
                  base=base, seed=n + variant)
 
 
-@pytest.mark.parametrize("variant", [49, 50, 55])
+@pytest.mark.parametrize("variant", [49, 50, 54, 55])
 @pytest.mark.parametrize("stride,length", [(1500, 1500), (1505, 1500), (1024, 1024), (1921, 1921), (1337, 1337)])
 def test_xcopy_fast_layout(eng, stride, length, variant):
-    """Copy-emit variants 49 / 50 (the transposed layout, natural / persistent grid) where its fast layout applies: every record of a
+    """Copy-emit variants 49 / 50 / 54 / 55 (the transposed layout: natural / persistent grid, non-temporal body
+    stores, body chunks re-dealt) where its fast layout applies: every record of a
     wavefront has its payload from inside the header window to the record's end (IPv4 / IPv6, UDP /
     TCP / ICMP, payloads at source offsets of every 4-byte phase); then the same batch with one record
     in 37 copying a shorter range, so that some wavefronts take the generic path.  Bit-exact
@@ -227,7 +228,7 @@ def test_xcopy_fast_layout(eng, stride, length, variant):
         _run(eng, recs, mixed, fixed_stride=stride, fixed_len=length, variant=variant, base=base, seed=n + 1)
 
 
-COPY_VARIANTS = [-1, 1, 8, 11, 16, 17, 21, 22, 30]
+COPY_VARIANTS = [-1, 1, 8, 11, 16, 17, 21, 22, 30, 98, 102]
 
 
 @pytest.mark.parametrize("variant", COPY_VARIANTS)
