@@ -226,7 +226,13 @@ int smol_csum_batch_data(smol_csum_ctx_t* ctx, const uint8_t* d_buf,
  * context's scratch, a second one writes the field segments, per 2^21 records): the context owns
  * ~17 MB of device scratch, allocated by smol_csum_ctx_create, and orders a staged emit issued on
  * another stream after the previous one (an event wait), so emits on one context may use several
- * streams.  No device memory is allocated by a batched call: the calls may be captured in a HIP
+ * streams.  Fixed-stride batches of 2^20 to 2^21 records of 1473-1921 bytes take the same two-launch
+ * shape through the same scratch (the first launch writes every record's smol_csum_fields_t entry
+ * there, the second the records, per 2^20 records) and are ordered across streams in the same way,
+ * except that the event is recorded on the previous stream only when a call on another stream
+ * arrives (if that stream has been destroyed by then, the device is synchronised instead); on a
+ * capturing stream they run as one launch and use neither the scratch nor an event.  No device
+ * memory is allocated by a batched call: the calls may be captured in a HIP
  * graph (a graph holding a staged emit uses the context's scratch when it replays: do not replay it
  * concurrently with another emit on the same context). */
 int smol_csum_batch_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* batch,

@@ -101,6 +101,20 @@ int smol_csum_tool_set_fields_kernel(smol_csum_ctx_t* ctx, int kernel);
  * reach it (the kernel has no variant number). */
 int smol_csum_tool_set_vcopy_stores(smol_csum_ctx_t* ctx, int nt);
 
+/* The two-launch route of fixed-stride whole-segment emit (csrc/csum_api.cpp run(); no variant number):
+ * a picked transposed-walk emit with whole field segments (variants 101 / 57) runs as the fields-sink
+ * form of the same kernel writing every record's entry into the context's entry buffer, followed by a
+ * segment pass that writes the records (csrc/csum_segpass.hip).  `route` -1 (the default): where the
+ * library's measured range says so; 0: always one launch; 1: the pair wherever it is legal, that is
+ * nothing forced (smol_csum_tool_set_variant), no descriptors, no SMOL_BATCH_FIELD_STORES, not a
+ * 6LoWPAN NHC call, and the stream not capturing. */
+int smol_csum_tool_set_emit_route(smol_csum_ctx_t* ctx, int route);
+/* 1 when this context's last smol_csum_batch_emit ran as the pair, else 0. */
+int smol_csum_tool_last_route(const smol_csum_ctx_t* ctx);
+/* Records per launch pair of the route (0: the default, as many entries as the buffer holds, 2^20;
+ * more is SMOL_EINVAL): lets a test put chunk seams into a small batch. */
+int smol_csum_tool_set_route_chunk(smol_csum_ctx_t* ctx, uint64_t records);
+
 /* Read-only HBM streaming probe over `bytes` (multiple of 16, 16-byte aligned `d_buf`): the
  * achievable read ceiling that the checksum kernels are compared with.  Each wavefront streams
  * contiguous 8-KiB pieces with eight non-temporal 16-byte loads per lane in flight (the fastest

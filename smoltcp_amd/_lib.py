@@ -48,13 +48,15 @@ TOOL_SYMBOLS = [
     "smol_csum_tool_kernel_name", "smol_csum_tool_kernel_for", "smol_csum_tool_last_launch",
     "smol_csum_tool_pick", "smol_csum_tool_variant_info", "smol_csum_tool_form",
     "smol_csum_tool_set_fields_kernel", "smol_csum_tool_walk_launch", "smol_csum_tool_set_vcopy_stores",
+    "smol_csum_tool_set_emit_route", "smol_csum_tool_last_route", "smol_csum_tool_set_route_chunk",
 ]
 # Tool symbols added in later rounds: bound only when the loaded build has them (SMOLCSUM_LIB may name
 # an older build for an A/B run), and a call to a missing one raises AttributeError naming it.
 OPTIONAL_TOOL_SYMBOLS = ("smol_csum_tool_variant_built", "smol_csum_tool_kernel_for", "smol_csum_tool_segment_probe",
                          "smol_csum_tool_pick", "smol_csum_tool_variant_info", "smol_csum_tool_form",
                          "smol_csum_tool_set_fields_kernel", "smol_csum_tool_walk_launch",
-                         "smol_csum_tool_set_vcopy_stores")
+                         "smol_csum_tool_set_vcopy_stores", "smol_csum_tool_set_emit_route",
+                         "smol_csum_tool_last_route", "smol_csum_tool_set_route_chunk")
 
 
 class SmolError(RuntimeError):
@@ -269,6 +271,9 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         "smol_csum_tool_set_fields_kernel": ([vp, i32], i32),
         "smol_csum_tool_walk_launch": ([i32, i32, i32, i32, i32, ctypes.POINTER(i32)], i32),
         "smol_csum_tool_set_vcopy_stores": ([vp, i32], i32),
+        "smol_csum_tool_set_emit_route": ([vp, i32], i32),
+        "smol_csum_tool_last_route": ([vp], i32),
+        "smol_csum_tool_set_route_chunk": ([vp, u64], i32),
     }
     assert set(optional) == set(OPTIONAL_TOOL_SYMBOLS)
     for name in OPTIONAL_TOOL_SYMBOLS:

@@ -29,12 +29,21 @@ struct smol_csum_ctx {
     uint64_t launch_records;  // records per kernel launch (0: the whole batch in one launch)
     // staged emit (the registry's V_STAGED variants): the field entries and per-8-record flags of one
     // chunk of kStageChunk records, allocated with the context (no allocation in a batched call);
-    // stage_stream / stage_done order a staged emit on another stream after the previous one
+    // stage_stream / stage_done order a use of the entries on another stream after the previous one
+    // (order_scratch below): stage_used says the entries have been used at all, stage_recorded that
+    // stage_done was recorded after their last use
     uint64_t* stage;
     uint32_t* stage_flags;
     void* stage_stream;
+    bool stage_used;
     bool stage_recorded;
     hipEvent_t stage_done;
+    // the two-launch route of fixed-stride whole-segment emit (run()): -1 automatic, 0 always one launch,
+    // 1 the pair wherever it is legal (smol_csum_tool_set_emit_route); records per launch pair (at most
+    // kRouteChunk, the entries the buffer holds); whether the last emit took the pair
+    int emit_route;
+    uint64_t route_chunk;
+    bool last_route;
     // descriptor-batch emit chooses between the staged form (kDwalkEmitStaged) and the in-place one
     // (kDwalkEmit) from the
     // previous staged call's wavefront flags (a sample of the first kSample copied to host memory):
@@ -209,6 +218,50 @@ bool capturing(hipStream_t s) {
     return hipStreamIsCapturing(s, &st) == hipSuccess && st != hipStreamCaptureStatusNone;
 }
 
+// Before the context's entry buffer is used on stream s: a use on another stream than the previous one
+// first waits for that one.  The staged descriptor emit records stage_done after every call; the
+// fixed-stride route does not (a record per call sits between the emit and the next kernel of a
+// single-stream caller, the common case), so the event is recorded here, on the previous stream, when a
+// call on a different stream arrives: after everything that stream holds by now, the last use of the
+// entries included.  If that record fails (the stream is gone), the device is synchronised instead.
+hipError_t order_scratch(smol_csum_ctx_t* ctx, void* stream) {
+    if (!ctx->stage_used || ctx->stage_stream == stream) return hipSuccess;
+    if (!ctx->stage_recorded) {
+        if (hipEventRecord(ctx->stage_done, (hipStream_t)ctx->stage_stream) != hipSuccess) {
+            (void)hipGetLastError();
+            ctx->stage_used = false;  // nothing is in flight after this
+            return hipDeviceSynchronize();
+        }
+        ctx->stage_recorded = true;
+    }
+    return hipStreamWaitEvent((hipStream_t)stream, ctx->stage_done, 0);
+}
+
+// The automatic route's range, from the interleaved on / off sweeps (profiles/
+// emit_route_sweep.jsonl): the record lengths and batch sizes at which the pair beat the one-launch form
+// by more than the spread of repeated runs, IPv4/UDP and the IPv6 mix.  Below 1473 B the pair loses
+// (1024 B: -12 %), and at 1922 B (4 records per wavefront) too; below 2^20 records the second launch's
+// fill and tail cost more than the stores save (2^18: -2 %, 2^19: even), and from 2^22 records on the chunk
+// pairs lose to one long launch (2^22: -2.9 %; C5's 2^27: -2.7 %).
+constexpr uint32_t kRouteMinLen = 1473, kRouteMaxLen = 1921;
+constexpr uint64_t kRouteMinRecords = 1ull << 20, kRouteMaxRecords = 1ull << 21;
+
+// Whether a picked emit runs as the two-launch route (stage 1: the fields-sink form of the picked kernel
+// into the context's entries; pass 2: csum_segpass.hip).  Only what pick_kernel chose by itself for a
+// plain fixed-stride batch, and never under capture: a captured emit keeps one launch and touches
+// neither the entries nor an event.
+bool takes_route(const smol_csum_ctx_t* ctx, int mode, const smol_csum_batch_t* b, const Pick& k, const uint8_t* d_addrs,
+                 hipStream_t s) {
+    if (mode != MODE_EMIT || ctx->emit_route == 0 || ctx->variant >= 0 || b->desc || d_addrs ||
+        (b->flags & SMOL_BATCH_FIELD_STORES) || k.family != F_XWALK ||
+        (k.variant != kXwalkEmitWT && k.variant != kXwalkEmitNt))
+        return false;
+    if (ctx->emit_route < 0 &&
+        (b->n < kRouteMinRecords || b->n > kRouteMaxRecords || b->len < kRouteMinLen || b->len > kRouteMaxLen))
+        return false;
+    return !capturing(s);
+}
+
 // Before a descriptor-batch emit: take the last staged call's sample when it has arrived (a
 // non-blocking event query), and probe with the staged form every kReprobe in-place calls.
 void update_desc_choice(smol_csum_ctx_t* ctx, hipStream_t s) {
@@ -275,14 +328,33 @@ int run(smol_csum_ctx_t* ctx, int mode, uint8_t* d_buf, const smol_csum_batch_t*
     const bool desc_auto = mode == MODE_EMIT && has_desc_auto(ctx, b, d_addrs);
     if (desc_auto) update_desc_choice(ctx, s);
     const Pick k = pick_kernel(pick_ctx(ctx), mode, b, p);
+    if (mode == MODE_EMIT) ctx->last_route = false;
+    if (takes_route(ctx, mode, b, k, d_addrs, s)) {
+        // route_chunk records at a time through the context's entries: each chunk's fields launch followed
+        // by its segment pass, in stream order
+        hipError_t e = order_scratch(ctx, stream);
+        if (e != hipSuccess) return hip_fail(e, "ordering the entry buffer (emit route)");
+        ctx->stage_stream = stream;
+        ctx->stage_used = true;
+        ctx->stage_recorded = false;
+        for (uint64_t i0 = 0; i0 < b->n; i0 += ctx->route_chunk) {
+            KParams q = p;
+            q.n = b->n - i0 < ctx->route_chunk ? b->n - i0 : ctx->route_chunk;
+            q.buf = d_buf + i0 * b->stride;
+            if (d_status) q.status = d_status + i0;
+            q.fields = reinterpret_cast<smol_csum_fields_t*>(ctx->stage);
+            e = launch_xwalk_route(k.variant, q, s);
+            if (e != hipSuccess) return hip_fail(e, "checksum kernel launch (emit route)");
+        }
+        ctx->last_route = true;
+        return SMOL_OK;
+    }
     if (mode == MODE_EMIT && variant_is(k.variant, V_STAGED)) {
         // staged emit: kStageChunk records at a time through the context's entries, each chunk's staging
         // launch followed by its segment pass.  A call on another stream than the previous staged emit
         // first waits for that one (the entries are the context's).
-        if (ctx->stage_recorded && ctx->stage_stream != stream) {
-            hipError_t ew = hipStreamWaitEvent(s, ctx->stage_done, 0);
-            if (ew != hipSuccess) return hip_fail(ew, "hipStreamWaitEvent (staged emit)");
-        }
+        const hipError_t ew = order_scratch(ctx, stream);
+        if (ew != hipSuccess) return hip_fail(ew, "hipStreamWaitEvent (staged emit)");
         for (uint64_t i0 = 0; i0 < b->n; i0 += kStageChunk) {
             KParams q = p;
             q.n = b->n - i0 < kStageChunk ? b->n - i0 : kStageChunk;
@@ -298,6 +370,7 @@ int run(smol_csum_ctx_t* ctx, int mode, uint8_t* d_buf, const smol_csum_batch_t*
         hipError_t er = hipEventRecord(ctx->stage_done, s);  // (after the sample's copy: it reads the flags)
         if (er != hipSuccess) return hip_fail(er, "hipEventRecord (staged emit)");
         ctx->stage_stream = stream;
+        ctx->stage_used = true;
         ctx->stage_recorded = true;
         return SMOL_OK;
     }
@@ -377,7 +450,11 @@ int smol_csum_ctx_create(int device, smol_csum_ctx_t** out) {
     c->stage = stage;
     c->stage_flags = flags;
     c->stage_stream = nullptr;
+    c->stage_used = false;
     c->stage_recorded = false;
+    c->emit_route = -1;
+    c->route_chunk = kRouteChunk;
+    c->last_route = false;
     c->stage_done = done;
     c->sample_host = sample;
     c->sample_ev = sev;
@@ -645,6 +722,20 @@ int smol_csum_tool_set_launch_records(smol_csum_ctx_t* ctx, uint64_t records) {
 int smol_csum_tool_set_fields_kernel(smol_csum_ctx_t* ctx, int kernel) {
     if (!ctx || kernel < FK_AUTO || kernel > FK_DWALK) return SMOL_EINVAL;
     ctx->fields_kernel = kernel;
+    return SMOL_OK;
+}
+
+int smol_csum_tool_set_emit_route(smol_csum_ctx_t* ctx, int route) {
+    if (!ctx || route < -1 || route > 1) return SMOL_EINVAL;
+    ctx->emit_route = route;
+    return SMOL_OK;
+}
+
+int smol_csum_tool_last_route(const smol_csum_ctx_t* ctx) { return ctx ? (ctx->last_route ? 1 : 0) : SMOL_EINVAL; }
+
+int smol_csum_tool_set_route_chunk(smol_csum_ctx_t* ctx, uint64_t records) {
+    if (!ctx || records > kRouteChunk) return SMOL_EINVAL;
+    ctx->route_chunk = records ? records : kRouteChunk;
     return SMOL_OK;
 }
 

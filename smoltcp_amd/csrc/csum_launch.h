@@ -284,6 +284,13 @@ template <bool IMPLICIT>
 hipError_t launch_walk_fields(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s);
 hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s);
 hipError_t launch_dwalk_fields(const KParams& p, hipStream_t s);
+// The two-launch route of fixed-stride whole-segment emit (run() takes it after pick_kernel has answered;
+// no registry row): stage 1 is launch_xwalk_fields' kernel writing into p.fields (the context's entry
+// buffer, which holds kRouteChunk entries), pass 2 the segment pass over those entries
+// (csum_segpass.hip seg_pass_fields_kernel; the rule: csum_segrule.h).
+constexpr uint64_t kRouteChunk = kStageChunk * sizeof(uint64_t) / sizeof(smol_csum_fields_t);
+hipError_t launch_xwalk_route(int variant, const KParams& p, hipStream_t s);
+hipError_t launch_seg_pass_fields(const KParams& p, hipStream_t s);
 
 // verify_copy (smol_csum_batch_verify_copy, csum_vcopy.hip): verify's parse, sums and gates, and each
 // record's L4 payload delivered to its slot of `dst` in the same pass.  Outside the variant registry.

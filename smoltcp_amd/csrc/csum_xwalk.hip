@@ -351,11 +351,8 @@ static void launch_xwalk_form(uint32_t blocks, const KParams& p, hipStream_t s) 
 
 // emit_fields' transposed form (XFields): R consecutive records finish in one wavefront, so their entries
 // leave as one run of R x 16 B (R = 8: a whole 128-B line per store instruction).
-hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s) {
-    const int R = xwalk_records(p.len);
-    if (R == 0 || !p.fields) return hipErrorInvalidValue;
+static hipError_t launch_fields_form(int R, const KParams& p, hipStream_t s) {
     const uint64_t per = (uint64_t)xwalk::WAVES * R;
-    note_launch(KERN_XWALK_FIELDS, 0, 64 / R, 16 / R);
     const uint64_t span = kMaxGridBlocks * per;  // as launch_xwalk: no grid-stride loop
     for (uint64_t i0 = 0; i0 < p.n; i0 += span) {
         KParams q = p;
@@ -373,6 +370,25 @@ hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s) {
         if (e != hipSuccess) return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s) {
+    const int R = xwalk_records(p.len);
+    if (R == 0 || !p.fields) return hipErrorInvalidValue;
+    note_launch(KERN_XWALK_FIELDS, 0, 64 / R, 16 / R);
+    return launch_fields_form(R, p, s);
+}
+
+// The two-launch route of a picked whole-segment emit (csum_api.cpp run() decides when; `variant` is the
+// pick, 101 or 57, which the launch record keeps): the same form with p.fields in the context's scratch,
+// then the segment pass over those entries (csum_segpass.hip), which writes the records and the status
+// bytes.  At most kRouteChunk records: run() chunks.
+hipError_t launch_xwalk_route(int variant, const KParams& p, hipStream_t s) {
+    const int R = xwalk_records(p.len);
+    if (R == 0 || !p.fields || p.desc || p.n > kRouteChunk) return hipErrorInvalidValue;
+    note_launch(KERN_XWALK, (uint32_t)variant, 64 / R, 16 / R);
+    const hipError_t e = launch_fields_form(R, p, s);
+    return e != hipSuccess ? e : launch_seg_pass_fields(p, s);
 }
 
 // (variant, mode) -> form: the registry's switch (csum_variants.h with_xwalk_form).

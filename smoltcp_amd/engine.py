@@ -514,6 +514,19 @@ class ChecksumEngine:
         3 the descriptor walk (a form that does not serve the batch gives way to the walk kernel)."""
         check(self._L.smol_csum_tool_set_fields_kernel(self._h, int(kernel)), "smol_csum_tool_set_fields_kernel")
 
+    def set_emit_route(self, route: int):
+        """Fixed-stride whole-segment emit as two launches (the fields-sink kernel into the context's entries,
+        then the segment pass): -1 where the library's measured range says so, 0 never, 1 wherever it is legal."""
+        check(self._L.smol_csum_tool_set_emit_route(self._h, int(route)), "smol_csum_tool_set_emit_route")
+
+    def last_route(self) -> bool:
+        """Whether this engine's last emit ran as the two-launch route."""
+        return bool(self._L.smol_csum_tool_last_route(self._h))
+
+    def set_route_chunk(self, records: int):
+        """Records per launch pair of the route (0: the default, what the entry buffer holds)."""
+        check(self._L.smol_csum_tool_set_route_chunk(self._h, int(records)), "smol_csum_tool_set_route_chunk")
+
     def set_vcopy_stores(self, nt: bool):
         """verify_copy's body stores: False the library's choice (the default cache policy), True non-temporal."""
         check(self._L.smol_csum_tool_set_vcopy_stores(self._h, int(bool(nt))), "smol_csum_tool_set_vcopy_stores")
