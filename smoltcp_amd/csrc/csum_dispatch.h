@@ -10,7 +10,7 @@
 namespace smolcsum {
 
 // The kernel a batched call runs: its family, variant and (walk / tile / copy kernels) launch shape.
-// One pure function, so that smol_csum_tool_kernel_for names exactly what run() launches.
+// One pure function, so that smol_csum_tool_kernel_for names exactly what run_one() (csum_api.cpp) launches.
 struct Pick {
     int family;
     int variant;
@@ -65,7 +65,7 @@ constexpr int kDwalkVerify = 63;
 // records 0.186 -> 0.183; its verify measured 0.4 % slower, so verify stays on 63
 // (profiles/r05_experiments/dwalk_cached_windows.txt).
 constexpr int kDwalkEmit = 41;
-// descriptor-batch emit while the records stage (round 6; see smol_csum_ctx in csum_api.cpp)
+// descriptor-batch emit while the records stage (round 6; see smol_csum_ctx in csum_ctx.h)
 constexpr int kDwalkEmitStaged = 97;
 // copy-emit: csum_copy.hip's variant 17 (body chunks = one source load + shift + sum + store) with the
 // first body round's loads issued ahead of round 1's stores, at its default shape (16 x 4): C2copy

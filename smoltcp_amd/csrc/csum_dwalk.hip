@@ -524,42 +524,26 @@ static hipError_t launch_dwalk_form(const KParams& p, hipStream_t s) {
 hipError_t launch_dwalk_fields(const KParams& p, hipStream_t s) {
     if (!p.fields) return hipErrorInvalidValue;
     note_launch(KERN_DWALK_FIELDS, 0, dwalk::G, dwalk::U);
-    const uint64_t span = kMaxGridBlocks * (uint64_t)dwalk::GPB;
-    for (uint64_t i0 = 0; i0 < p.n; i0 += span) {
-        KParams q = p;
-        q.n = p.n - i0 < span ? p.n - i0 : span;
-        if (p.desc) q.desc = p.desc + i0;
-        else q.buf = p.buf + i0 * p.stride;
-        q.fields = p.fields + i0;
+    return for_chunks(p, kMaxGridBlocks * (uint64_t)dwalk::GPB, [&](uint64_t, const KParams& q) {
         const uint32_t b = grid_blocks((q.n + dwalk::GPB - 1) / dwalk::GPB, kMaxGridBlocks);
         hipLaunchKernelGGL((dwalk_kernel<MODE_EMIT, false, true, DW_WIN_CACHED | DW_FIELDS_OUT>), dim3(b), dim3(256), 0, s, q);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_dwalk(int mode, int variant, const KParams& p, hipStream_t s) {
     if (mode != MODE_EMIT && mode != MODE_VERIFY) return hipErrorInvalidValue;
-    // staged: one staging launch and its segment pass over at most kStageChunk records (run() chunks)
+    // staged: one staging launch and its segment pass over at most kStageChunk records (run_one() chunks)
     const bool staged = mode == MODE_EMIT && variant_is(variant, V_STAGED);
     if (staged && (!p.stage || !p.stage_flags || p.n > kStageChunk)) return hipErrorInvalidValue;
     note_launch(KERN_DWALK, (uint32_t)variant, dwalk::G, dwalk::U);
-    const uint64_t span = kMaxGridBlocks * (uint64_t)dwalk::GPB;
-    for (uint64_t i0 = 0; i0 < p.n; i0 += span) {
-        KParams q = p;
-        q.n = p.n - i0 < span ? p.n - i0 : span;
-        if (p.desc) q.desc = p.desc + i0;
-        else q.buf = p.buf + i0 * p.stride;
-        if (p.status) q.status = p.status + i0;
+    return for_chunks(p, kMaxGridBlocks * (uint64_t)dwalk::GPB, [&](uint64_t, const KParams& q) {
         hipError_t e = hipSuccess;
         const bool known =
             mode == MODE_EMIT ? with_dwalk_form<true>(variant, [&](auto f) { e = launch_dwalk_form<MODE_EMIT, decltype(f)>(q, s); })
                               : with_dwalk_form<false>(variant, [&](auto f) { e = launch_dwalk_form<MODE_VERIFY, decltype(f)>(q, s); });
-        if (!known) return hipErrorInvalidValue;  // not a descriptor-walk variant of this library
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return known ? e : hipErrorInvalidValue;  // (not a descriptor-walk variant of this library)
+    });
 }
 
 }  // namespace smolcsum

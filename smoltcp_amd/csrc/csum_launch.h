@@ -190,6 +190,35 @@ struct KParams {
     smol_csum_fields_t* fields;  // emit_fields: one 16-B entry per record (the kernels write nothing else)
 };
 
+// p over the records [i0, i0 + n): n, the batch (desc when set, else buf) and every per-record array that
+// is set (status, out16, copy, addrs, fields) advanced to record i0; null stays null.  The rest is left
+// alone: dummy and src are not indexed by record, and stage / stage_flags hold one chunk's entries, which
+// the segment pass indexes from 0, so whoever cuts chunks attaches them after slicing.
+inline KParams slice(const KParams& p, uint64_t i0, uint64_t n) {
+    KParams q = p;
+    q.n = n;
+    if (p.desc) q.desc = p.desc + i0;
+    else q.buf = p.buf + i0 * p.stride;
+    if (p.status) q.status = p.status + i0;
+    if (p.out16) q.out16 = p.out16 + i0;
+    if (p.copy) q.copy = p.copy + i0;
+    if (p.addrs) q.addrs = p.addrs + 32 * i0;
+    if (p.fields) q.fields = p.fields + i0;
+    return q;
+}
+
+// fn(i0, slice of p) over consecutive chunks of at most `per` records (0: the whole batch), in order;
+// stops at the first result that is not zero (hipSuccess, SMOL_OK) and returns it.
+template <class Fn>
+inline auto for_chunks(const KParams& p, uint64_t per, Fn&& fn) -> decltype(fn(uint64_t{}, p)) {
+    if (per == 0 || per > p.n) per = p.n;
+    for (uint64_t i0 = 0; i0 < p.n; i0 += per) {
+        const auto r = fn(i0, slice(p, i0, p.n - i0 < per ? p.n - i0 : per));
+        if (r != decltype(r){}) return r;
+    }
+    return {};
+}
+
 // The 8 XCDs of an MI355X are dealt workgroups round-robin (MI355X_MICROARCH.md, workgroup dispatch:
 // observed, not promised): blocks b, b + 8, ... share an XCD.  This bijection on [0, nwg) gives the
 // blocks of one XCD a contiguous range of logical blocks, so that each XCD streams its own part of
@@ -284,8 +313,8 @@ template <bool IMPLICIT>
 hipError_t launch_walk_fields(int shape, const KParams& p, uint32_t max_blocks, hipStream_t s);
 hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s);
 hipError_t launch_dwalk_fields(const KParams& p, hipStream_t s);
-// The two-launch route of fixed-stride whole-segment emit (run() takes it after pick_kernel has answered;
-// no registry row): stage 1 is launch_xwalk_fields' kernel writing into p.fields (the context's entry
+// The two-launch route of fixed-stride whole-segment emit (csum_api.cpp run_one() takes it after pick_kernel
+// has answered; no registry row): stage 1 is launch_xwalk_fields' kernel writing into p.fields (the context's entry
 // buffer, which holds kRouteChunk entries), pass 2 the segment pass over those entries
 // (csum_segpass.hip seg_pass_fields_kernel; the rule: csum_segrule.h).
 constexpr uint64_t kRouteChunk = kStageChunk * sizeof(uint64_t) / sizeof(smol_csum_fields_t);

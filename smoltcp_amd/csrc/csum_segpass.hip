@@ -1,4 +1,4 @@
-// The segment pass of the two-launch fixed-stride emit (the route of csum_api.cpp run(): stage 1 is
+// The segment pass of the two-launch fixed-stride emit (the route of csum_api.cpp run_one(): stage 1 is
 // xwalk_kernel<MODE_EMIT, R, XFields> writing every record's emit_fields entry into the context's scratch,
 // this pass writes the records).  seg_pass4_kernel (csum_dwalk.hip) serves the staged descriptor emit with
 // one record per lane group and three dependent loads (flag, entry, segment); here stage 1 writes every

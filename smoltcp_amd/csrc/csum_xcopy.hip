@@ -299,18 +299,11 @@ hipError_t launch_xcopy(int variant, const KParams& p, hipStream_t s) {
             hipLaunchKernelGGL((xcopy_kernel<F>), dim3(b), dim3(256), 0, s, p);
             e = hipGetLastError();
         } else {
-            const uint64_t span = kMaxGridBlocks * per;
-            e = hipSuccess;
-            for (uint64_t i0 = 0; i0 < p.n && e == hipSuccess; i0 += span) {
-                KParams q = p;
-                q.n = p.n - i0 < span ? p.n - i0 : span;
-                q.buf = p.buf + i0 * p.stride;
-                q.copy = p.copy + i0;
-                if (p.status) q.status = p.status + i0;
+            e = for_chunks(p, kMaxGridBlocks * per, [&](uint64_t, const KParams& q) {
                 const uint32_t b = grid_blocks((q.n + per - 1) / per, kMaxGridBlocks);
                 hipLaunchKernelGGL((xcopy_kernel<F>), dim3(b), dim3(256), 0, s, q);
-                e = hipGetLastError();
-            }
+                return hipGetLastError();
+            });
         }
     });
 #endif

@@ -353,12 +353,8 @@ static void launch_xwalk_form(uint32_t blocks, const KParams& p, hipStream_t s) 
 // leave as one run of R x 16 B (R = 8: a whole 128-B line per store instruction).
 static hipError_t launch_fields_form(int R, const KParams& p, hipStream_t s) {
     const uint64_t per = (uint64_t)xwalk::WAVES * R;
-    const uint64_t span = kMaxGridBlocks * per;  // as launch_xwalk: no grid-stride loop
-    for (uint64_t i0 = 0; i0 < p.n; i0 += span) {
-        KParams q = p;
-        q.n = p.n - i0 < span ? p.n - i0 : span;
-        q.buf = p.buf + i0 * p.stride;
-        q.fields = p.fields + i0;
+    // as launch_xwalk: no grid-stride loop
+    return for_chunks(p, kMaxGridBlocks * per, [&](uint64_t, const KParams& q) {
         const uint32_t b = grid_blocks((q.n + per - 1) / per, kMaxGridBlocks);
         switch (R) {
             case 8: launch_xwalk_form<MODE_EMIT, 8, XFields>(b, q, s); break;
@@ -366,10 +362,8 @@ static hipError_t launch_fields_form(int R, const KParams& p, hipStream_t s) {
             case 2: launch_xwalk_form<MODE_EMIT, 2, XFields>(b, q, s); break;
             default: launch_xwalk_form<MODE_EMIT, 1, XFields>(b, q, s); break;
         }
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s) {
@@ -379,10 +373,10 @@ hipError_t launch_xwalk_fields(const KParams& p, hipStream_t s) {
     return launch_fields_form(R, p, s);
 }
 
-// The two-launch route of a picked whole-segment emit (csum_api.cpp run() decides when; `variant` is the
+// The two-launch route of a picked whole-segment emit (csum_api.cpp run_one() decides when; `variant` is the
 // pick, 101 or 57, which the launch record keeps): the same form with p.fields in the context's scratch,
 // then the segment pass over those entries (csum_segpass.hip), which writes the records and the status
-// bytes.  At most kRouteChunk records: run() chunks.
+// bytes.  At most kRouteChunk records: run_one() chunks.
 hipError_t launch_xwalk_route(int variant, const KParams& p, hipStream_t s) {
     const int R = xwalk_records(p.len);
     if (R == 0 || !p.fields || p.desc || p.n > kRouteChunk) return hipErrorInvalidValue;
@@ -407,12 +401,7 @@ hipError_t launch_xwalk(int mode, int variant, const KParams& p, hipStream_t s) 
     note_launch(KERN_XWALK, (uint32_t)variant, 64 / R, 16 / R);
     // one workgroup per 4R records and no grid-stride loop: a batch past kMaxGridBlocks workgroups
     // (more records than 288 GB of HBM holds at these lengths) goes out as several launches
-    const uint64_t span = kMaxGridBlocks * per;
-    for (uint64_t i0 = 0; i0 < p.n; i0 += span) {
-        KParams q = p;
-        q.n = p.n - i0 < span ? p.n - i0 : span;
-        q.buf = p.buf + i0 * p.stride;
-        if (p.status) q.status = p.status + i0;
+    return for_chunks(p, kMaxGridBlocks * per, [&](uint64_t, const KParams& q) {
         const uint32_t b = grid_blocks((q.n + per - 1) / per, kMaxGridBlocks);
         bool known;
         switch (R) {
@@ -422,14 +411,10 @@ hipError_t launch_xwalk(int mode, int variant, const KParams& p, hipStream_t s) 
             default: known = launch_xwalk_r<1>(mode, variant, b, q, s); break;
         }
         if (!known) return hipErrorInvalidValue;  // not a transposed-walk variant of this library
-        hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return e;
-        if (staged) {  // the segment pass follows the staging launch
-            e = launch_seg_pass(q, s);
-            if (e != hipSuccess) return e;
-        }
-    }
-    return hipSuccess;
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess || !staged) return e;
+        return launch_seg_pass(q, s);  // the segment pass follows the staging launch
+    });
 }
 
 }  // namespace smolcsum

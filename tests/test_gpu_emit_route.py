@@ -1,5 +1,5 @@
 """GPU: the two-launch route of fixed-stride whole-segment emit (the fields-sink kernel into the context's
-entries, then the segment pass: csrc/csum_api.cpp run(), csrc/csum_segpass.hip) against the CPU oracle.
+entries, then the segment pass: csrc/csum_api.cpp run_one(), csrc/csum_segpass.hip) against the CPU oracle.
 
 Every case runs smol_csum_batch_emit with the route forced on (set_emit_route(1)) and compares the WHOLE
 tensor, 128 random guard bytes on each side, the bytes between the tensor's start and the batch, the
@@ -217,6 +217,54 @@ def test_two_streams(eng):
     torch.cuda.synchronize()
     for a, b in bufs:
         assert torch.equal(a, want_a) and torch.equal(b, want_b)
+
+
+def test_launch_records_across_route(eng):
+    """launch_records 40 over 100 records: sub-batches of 40, 40 and 20, each with its own choice of kernel and
+    its own route chunks (16: seams at 16, 32 and 40 inside each).  Bytes and status against the oracle and the
+    route-off run (which goes out as three launches too); last_route reports the last sub-batch."""
+    eng.set_launch_records(40)
+    try:
+        for length, stride in ((1500, 1500), (1100, 1164)):
+            assert _route_row(length, stride, 40) and _route_row(length, stride, 20)
+            lay = Layout(eng, length, stride, E.SYNTH_V6MIX, seed=41)
+            for place in (0, 36):
+                _check(eng, lay, NMAX, place, chunk=16, tag="launch_records")  # (asserts last_route with the route on)
+    finally:
+        eng.set_launch_records(0)
+
+
+def test_two_scratch_users_two_streams(eng):
+    """The entry buffer's two users, the staged descriptor emit (variant 97, forced: it takes no sample) and
+    the fixed-stride route, alternate on two streams of one context with nothing ordering them, the streams
+    swapped in odd rounds: every buffer matches the oracle's emit."""
+    la, lb = Layout(eng, 1087, 1087, E.SYNTH_V6MIX, seed=51), Layout(eng, 1500, 1500, E.SYNTH_UDP4, seed=52)
+    wa, want_a, sa = la.tensor(60, NMAX)
+    wb, want_b, sb = lb.tensor(4, NMAX)
+    s1, s2 = torch.cuda.Stream(), torch.cuda.Stream()
+    bufs = [(wa.clone(), wb.clone()) for _ in range(6)]
+    offs = np.arange(NMAX, dtype=np.uint64) * la.stride
+    ba = E.Batch.from_records(offs, np.full(NMAX, la.length), E.KIND_IP, "cuda:0")
+    bb = E.Batch.fixed(NMAX, lb.stride, lb.length, E.KIND_IP)
+    torch.cuda.synchronize()  # the buffers and descriptors are ready; nothing orders the calls below
+    eng.set_emit_route(1)
+    try:
+        for r, (a, b) in enumerate(bufs):
+            first, second = (s1, s2) if r % 2 == 0 else (s2, s1)
+            eng.set_variant(97)
+            eng.emit(a[sa:sa + NMAX * la.stride], ba, stream=first)
+            launched = eng.last_launch()
+            assert launched["kernel"] == "dwalk_kernel" and launched["variant"] == 97 and not eng.last_route(), (r, launched)
+            eng.set_variant(-1)
+            eng.emit(b[sb:sb + NMAX * lb.stride], bb, stream=second)
+            assert eng.last_route(), r
+    finally:
+        eng.set_variant(-1)
+        eng.set_emit_route(-1)
+    torch.cuda.synchronize()
+    for r, (a, b) in enumerate(bufs):
+        assert torch.equal(a, want_a), (r, "staged descriptor emit")
+        assert torch.equal(b, want_b), (r, "route")
 
 
 def test_capture_keeps_one_launch(eng):

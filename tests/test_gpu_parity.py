@@ -675,7 +675,7 @@ def _kv(launched):
 
 def _expected_launch(variant, op, has_desc):
     """The kernel instantiation a forced `variant` must run (csum_walk.h launch_walk, csum_api.cpp
-    run): (kernel, VAR template argument)."""
+    run_one): (kernel, VAR template argument)."""
     if variant in (3, 4, 7):
         return ("csum_tile_kernel", {3: 0, 4: 1, 7: 2}[variant])
     emit_fixed = op == "emit" and not has_desc

@@ -119,8 +119,8 @@ def test_last_launch_families(eng):
 
 
 def test_kernel_for_names_the_launch(eng):
-    """smol_csum_tool_kernel_for (csum_api.cpp pick_kernel, the decision run() launches) names the kernel
-    every fixed-stride length, descriptor batch and forced variant actually ran (last_launch)."""
+    """smol_csum_tool_kernel_for (csum_tools.cpp; csum_dispatch.h pick_kernel, the decision csum_api.cpp
+    run_one() launches) names the kernel every fixed-stride length, descriptor batch and forced variant actually ran (last_launch)."""
     cases = [(LL, stride, op) for LL, stride in ((1320, 1320), (1500, 1500), (1500, 1564), (1600, 1600), (2500, 2500),
                                                  (9000, 9000), (12000, 12000), (1024, 1024), (1700, 1764))
              for op in ("emit", "verify", "data")]

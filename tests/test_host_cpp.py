@@ -70,6 +70,27 @@ def test_grid_orders_bijective(binary):
     assert r.returncode == 0 and "grid orders ok" in r.stdout, r.stdout + r.stderr
 
 
+def test_slice_and_chunks(binary):
+    """Cutting a record range out of a batch (csum_launch.h slice / for_chunks, the one helper behind
+    launch_records, the route's and the staged emit's chunks and the launchers' grid spans): the pointer
+    arithmetic of each per-record array, null staying null, the chunk loop's order and its stop at the first
+    failure (tests/cpp/test_slice.cpp, a host build of the same header)."""
+    r = subprocess.run([os.path.join(CPP, "test_slice")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "slices ok" in r.stdout, r.stdout + r.stderr
+
+
+def test_slice_and_chunks_asan(binary):
+    """The same program, stand-alone, under ASan + UBSan (the SAN flags of tests/cpp/Makefile): any report
+    aborts it."""
+    import fcntl
+
+    with open(os.path.join(CPP, ".make.lock"), "w") as lk:
+        fcntl.flock(lk, fcntl.LOCK_EX)
+        subprocess.run(["make", "-s", "-C", CPP, "test_slice_asan"], check=True, timeout=300)
+    r = subprocess.run([os.path.join(CPP, "test_slice_asan")], capture_output=True, text=True, timeout=120)
+    assert r.returncode == 0 and "slices ok" in r.stdout, r.stdout + r.stderr
+
+
 def test_cpp_engine_fails_loudly_without_device(binary):
     if _has_gpu():
         pytest.skip("a GPU is present")
