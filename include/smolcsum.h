@@ -31,6 +31,8 @@
  *         the fragment payloads put together in the datagram's slot (the reassembler's copy);
  *       - smol_csum_batch_fragment_emit == emit over whole IPv4 datagrams, and in the same pass each
  *         datagram cut into the frames the iface sends (dispatch_ip's and dispatch_ipv4_frag's copy);
+ *       - smol_csum_batch_tcp_segment_emit == emit over TCP header templates, and in the same pass each
+ *         send's payload cut into MSS-sized segments behind them (TcpSocket::dispatch's burst);
  *       - smol_csum_batch_data   == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
@@ -578,6 +580,98 @@ int smol_csum_batch_fragment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf, co
                                   const smol_checksum_caps_t* caps, uint8_t* d_dst,
                                   const smol_csum_fragplan_t* d_plans, uint32_t frame_stride,
                                   smol_csum_fragout_t* d_out, void* stream);
+
+/* One send (32 bytes, 16-byte-aligned device array, input; one per record). */
+typedef struct {
+    uint64_t src_offset; /* first payload byte in d_src (any alignment)            */
+    uint32_t len;        /* payload bytes of the whole send (0: one bare segment)  */
+    uint16_t mss;        /* payload bytes per segment; 0: the record is not cut    */
+    uint16_t reserved;   /* 0; the kernel ignores it                               */
+    uint64_t dst_offset; /* first frame in d_dst (any alignment)                   */
+    uint32_t cap;        /* bytes available there                                  */
+    uint32_t reserved2;  /* 0; ignored                                             */
+} smol_csum_tcpplan_t;
+
+/* What became of one send (16 bytes, 16-byte-aligned device array, output; one per record): the layout of
+ * smol_csum_fragout_t under its own name. */
+typedef struct {
+    uint32_t count;     /* frames the send makes (0: not a template this call cuts)                  */
+    uint32_t frame_len; /* bytes of every frame but the last: hl + min(mss, len)                     */
+    uint32_t last_len;  /* bytes of the last frame (count == 1: the only one)                        */
+    uint8_t status;     /* the byte smol_csum_batch_emit puts in d_status for the record             */
+    uint8_t written;    /* 1: all count frames were stored                                           */
+    uint16_t reserved;  /* 0 */
+} smol_csum_tcpout_t;
+
+/* emit, and every TCP send cut into MSS-sized segments, in one pass over the payload: the TCP counterpart
+ * of smol_csum_batch_fragment_emit (one header template and one payload range in, the iface's frames out,
+ * every checksum filled).  In the reference such a burst is repeated TcpSocket::dispatch calls within one
+ * poll: each takes tx_buffer.get_allocated(offset, size) with size <= effective_mss
+ * (src/socket/tcp.rs:2620-2673) and sets PSH or FIN only when the segment reaches the end of the buffer
+ * (tcp.rs:2675-2687); TcpRepr::emit then copies the payload and fill_checksum sums it
+ * (src/wire/tcp.rs:1087-1095, 616-626), and the IP header goes in front of each one (Ipv4Repr::emit,
+ * src/wire/ipv4.rs:584-611, which writes ident 0 and DF on every packet; Ipv6Repr::emit,
+ * src/wire/ipv6.rs:628-640).  Between two segments of such a burst only the sequence number, the IP
+ * length field, FIN / PSH and the two checksums change.  Here each payload byte is read once and each
+ * frame byte written once.
+ *
+ * Records.  Each record of the batch (fixed-stride or descriptors) is one header template: what the stack
+ * emits for a TCP segment with an empty payload.  An optional Ethernet header (SMOL_KIND_ETH, io = 14;
+ * SMOL_KIND_IP, io = 0), an IPv4 or IPv6 header, and a TCP header with its options, thl = 4 * data offset:
+ * hl = io + 20|40 + thl, so hl <= 114.  Record bytes past hl are ignored.  d_buf is only read.
+ *
+ * Which records are cut.  Let g be emit's parse of the record.  A record is cut when all of these hold:
+ *   - g reports no status bit (the record passes every check_len emit runs) and the protocol is TCP;
+ *   - IPv4 with IHL 5, or IPv6 whose next header is 6 directly (a template with a Hop-by-Hop header is
+ *     not cut);
+ *   - the L4 length the IP header states equals thl: the template carries no payload of its own;
+ *   - SYN and RST are clear (the stack sends those without data, through plain emit);
+ *   - mss >= 1;
+ *   - the largest frame's IP length field fits 16 bits: IPv4 20 + thl + min(mss, len) <= 65535, IPv6
+ *     thl + min(mss, len) <= 65535.
+ * Every other record (SMOL_REC_IPHDR_ONLY; fragments; UDP and the other protocols; SMOL_KIND_RAW; non-IP
+ * ethertypes; a failed check_len) gets count = 0, written = 0 and nothing stored.  status is always the
+ * byte smol_csum_batch_emit reports for the record as it stands.
+ *
+ * Cut.  count = max(1, ceil(len / mss)); p_k = min(mss, len - k * mss) (p_0 = 0 when len == 0);
+ * frame_len = hl + p_0; last_len = hl + p_{count-1}; S = frame_stride, or frame_len when
+ * frame_stride == 0; frame k starts at d_dst + dst_offset + k * S.  Frame k is the template's first hl
+ * bytes with the following changes, followed by d_src[src_offset + k * mss ..][.. p_k]:
+ *   - IPv4: total length is 20 + thl + p_k; the header checksum is filled under caps.ipv4.tx(), else 0;
+ *     ident, flags and TTL are as in the template on every frame (ipv4.rs:595-600);
+ *   - IPv6: payload length is thl + p_k;
+ *   - TCP sequence number: seq0 + k * mss mod 2^32;
+ *   - TCP flags: FIN and PSH are cleared on every frame but the last; every other flag bit is kept as in
+ *     the template on every frame;
+ *   - ack number, window, urgent pointer and options are verbatim on every frame;
+ *   - TCP checksum: under caps.tcp.tx() it covers the pseudo-header (length thl + p_k), the header and the
+ *     payload, with no 0 mapping (tcp.rs:616-626); otherwise it is 0.
+ * In short, frame k is byte for byte what smol_csum_batch_emit leaves in a record made of those rewritten
+ * headers followed by that payload slice, and what smol_csum_batch_copy_emit writes from host-built
+ * headers.
+ *
+ * Cap and stride.  The send needs (count - 1) * S + last_len bytes.  When that exceeds cap, or when
+ * frame_stride != 0 && frame_stride < frame_len, nothing is stored and written = 0; count, frame_len
+ * and last_len are still reported, so the caller can size a retry.  Gaps between frames
+ * (frame_stride > frame length) are never written.
+ *
+ * Reads and writes.  No byte of d_dst is ever read and none outside the frames of a written send is ever
+ * written; every byte of a written frame is written exactly once.  Edges go out as byte-masked stores,
+ * never read-modify-write, so slots and frames may lie back to back at any alignment.  d_src is only
+ * read, and only in 16-byte chunks that hold at least one byte of a cut plan's range.  d_src, d_dst and
+ * the batch must not overlap; slots must not overlap each other.
+ *
+ * Resources.  No context scratch, no event, no allocation; stream-ordered on `stream`, and calls on
+ * different streams are independent (also on one context).
+ *
+ * SMOL_EINVAL: NULL ctx, bad caps, NULL d_src / d_dst / d_plans / d_out with n > 0, d_plans or d_out not
+ * 16-byte aligned.  SMOL_ERANGE: as emit.  n == 0 returns SMOL_OK and launches nothing.
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive, as fragment_emit was). */
+int smol_csum_batch_tcp_segment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
+                                     const smol_checksum_caps_t* caps, const uint8_t* d_src, uint8_t* d_dst,
+                                     const smol_csum_tcpplan_t* d_plans, uint32_t frame_stride,
+                                     smol_csum_tcpout_t* d_out, void* stream);
 
 /* ---- 4. 6LoWPAN next-header-compressed UDP (RFC 6282 §4.3) ------------------------------- */
 

@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "smol_csum_batch_verify_copy",
     "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
     "smol_csum_batch_verify_frag", "smol_csum_batch_verify_reassemble", "smol_csum_batch_fragment_emit",
-    "smol_csum_batch_nhc_udp_emit",
+    "smol_csum_batch_tcp_segment_emit", "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
 ]
 TOOL_SYMBOLS = [
@@ -165,6 +165,33 @@ class FragOutC(ctypes.Structure):
     ]
 
 
+class TcpPlanC(ctypes.Structure):
+    """smol_csum_tcpplan_t: one send's payload range, MSS and place (smol_csum_batch_tcp_segment_emit)."""
+
+    _fields_ = [
+        ("src_offset", ctypes.c_uint64),
+        ("len", ctypes.c_uint32),
+        ("mss", ctypes.c_uint16),
+        ("reserved", ctypes.c_uint16),
+        ("dst_offset", ctypes.c_uint64),
+        ("cap", ctypes.c_uint32),
+        ("reserved2", ctypes.c_uint32),
+    ]
+
+
+class TcpOutC(ctypes.Structure):
+    """smol_csum_tcpout_t: what became of one send (smol_csum_batch_tcp_segment_emit)."""
+
+    _fields_ = [
+        ("count", ctypes.c_uint32),
+        ("frame_len", ctypes.c_uint32),
+        ("last_len", ctypes.c_uint32),
+        ("status", ctypes.c_uint8),
+        ("written", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint16),
+    ]
+
+
 _LIBS = {}
 
 
@@ -227,6 +254,10 @@ def lib(path: str | None = None) -> ctypes.CDLL:
     if hasattr(L, "smol_csum_batch_fragment_emit"):
         L.smol_csum_batch_fragment_emit.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps), vp, vp, u32, vp, vp]
         L.smol_csum_batch_fragment_emit.restype = i32
+    if hasattr(L, "smol_csum_batch_tcp_segment_emit"):
+        L.smol_csum_batch_tcp_segment_emit.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps), vp, vp, vp, u32,
+                                                       vp, vp]
+        L.smol_csum_batch_tcp_segment_emit.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []

@@ -433,6 +433,22 @@ int smol_csum_batch_fragment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf, co
     return on_device(ctx, "fragment_emit kernel launch", [&] { return launch_fragcut(p, v, (hipStream_t)stream); });
 }
 
+// Every send's header template and payload range cut into MSS-sized frames in its place of d_dst, checksums
+// filled in the same pass (include/smolcsum.h).  Uses none of the context's scratch or events, so calls on
+// different streams are independent.
+int smol_csum_batch_tcp_segment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
+                                     const smol_checksum_caps_t* caps, const uint8_t* d_src, uint8_t* d_dst,
+                                     const smol_csum_tcpplan_t* d_plans, uint32_t frame_stride,
+                                     smol_csum_tcpout_t* d_out, void* stream) {
+    int rc;
+    if (!begin_call(ctx, caps, b, d_buf, &rc)) return rc;
+    if (!d_src || !d_dst || !d_plans || !d_out || ((uintptr_t)d_plans & 15u) != 0 || ((uintptr_t)d_out & 15u) != 0)
+        return SMOL_EINVAL;
+    const KParams p = base_params(ctx, d_buf, b, caps);
+    const TcpCutArgs v = {d_src, d_dst, d_plans, frame_stride, d_out};
+    return on_device(ctx, "tcp_segment_emit kernel launch", [&] { return launch_tcpcut(p, v, (hipStream_t)stream); });
+}
+
 // ---- 6LoWPAN NHC UDP --------------------------------------------------------------------------
 
 int smol_csum_batch_nhc_udp_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,

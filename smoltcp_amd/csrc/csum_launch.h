@@ -255,10 +255,11 @@ __device__ inline uint64_t logical_block(uint32_t xcd_remap) {
 // non-temporal ones).
 // KERN_FRAGCOPY: smol_csum_batch_verify_reassemble's kernel (no registry row; variant 0, G 64, U its chunks per lane).
 // KERN_FRAGCUT: smol_csum_batch_fragment_emit's kernel (the same).
+// KERN_TCPCUT: smol_csum_batch_tcp_segment_emit's kernel (the same).
 enum {
     KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6,
     KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9, KERN_VCOPY = 10,
-    KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12
+    KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12, KERN_TCPCUT = 13
 };
 inline std::atomic<uint32_t> g_last_launch{0};
 inline void note_launch(uint32_t kern, uint32_t var, uint32_t g, uint32_t u) {
@@ -367,6 +368,17 @@ struct FragCutArgs {
     smol_csum_fragout_t* out;           // one 16-B entry per record (output)
 };
 hipError_t launch_fragcut(const KParams& p, const FragCutArgs& v, hipStream_t s);
+// tcp_segment_emit (smol_csum_batch_tcp_segment_emit, csum_tcpcut.hip): every send's header template and
+// payload range cut into MSS-sized frames in its place of `dst`, each frame's checksums filled in the same
+// pass.  One wavefront per send; outside the variant registry.
+struct TcpCutArgs {
+    const uint8_t* src;                // payload source buffer
+    uint8_t* dst;
+    const smol_csum_tcpplan_t* plans;  // one 32-B entry per record (input)
+    uint32_t frame_stride;             // 0: frames back to back
+    smol_csum_tcpout_t* out;           // one 16-B entry per record (output)
+};
+hipError_t launch_tcpcut(const KParams& p, const TcpCutArgs& v, hipStream_t s);
 hipError_t launch_stream_read(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t max_blocks,
                               hipStream_t s);
 hipError_t launch_field_probe(uint8_t* buf, uint64_t bytes, uint64_t stride, uint32_t f1, uint32_t f2,

@@ -16,7 +16,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import NO_FIELD, BatchC, Caps, DgramC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, check, lib
+from ._lib import (NO_FIELD, BatchC, Caps, DgramC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, TcpOutC, TcpPlanC, check,
+                   lib)
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -69,6 +70,13 @@ assert FRAGPLAN_DTYPE.itemsize == 16 == ctypes.sizeof(FragPlanC)
 FRAGOUT_DTYPE = np.dtype([("count", "<u4"), ("frame_len", "<u4"), ("last_len", "<u4"), ("status", "u1"), ("written", "u1"),
                           ("reserved", "<u2")])
 assert FRAGOUT_DTYPE.itemsize == 16 == ctypes.sizeof(FragOutC)
+# smol_csum_tcpplan_t / smol_csum_tcpout_t: one send's cut and what became of it (smol_csum_batch_tcp_segment_emit)
+TCPPLAN_DTYPE = np.dtype([("src_offset", "<u8"), ("len", "<u4"), ("mss", "<u2"), ("reserved", "<u2"), ("dst_offset", "<u8"),
+                          ("cap", "<u4"), ("reserved2", "<u4")])
+assert TCPPLAN_DTYPE.itemsize == 32 == ctypes.sizeof(TcpPlanC)
+TCPOUT_DTYPE = np.dtype([("count", "<u4"), ("frame_len", "<u4"), ("last_len", "<u4"), ("status", "u1"), ("written", "u1"),
+                         ("reserved", "<u2")])
+assert TCPOUT_DTYPE.itemsize == 16 == ctypes.sizeof(TcpOutC)
 
 
 def make_slots(dst_offsets, caps) -> np.ndarray:
@@ -88,6 +96,18 @@ def make_fragplans(dst_offsets, caps, ip_mtus, idents) -> np.ndarray:
     p["cap"] = np.broadcast_to(np.asarray(caps, dtype=np.uint32), (n,))
     p["ip_mtu"] = np.broadcast_to(np.asarray(ip_mtus, dtype=np.uint16), (n,))
     p["ident"] = np.broadcast_to(np.asarray(idents, dtype=np.uint16), (n,))
+    return p
+
+
+def make_tcpplans(src_offsets, lens, msss, dst_offsets, caps) -> np.ndarray:
+    """Host array of smol_csum_tcpplan_t (view it as uint8 and copy it to the device)."""
+    n = len(src_offsets)
+    p = np.zeros(n, dtype=TCPPLAN_DTYPE)
+    p["src_offset"] = np.asarray(src_offsets, dtype=np.uint64)
+    p["len"] = np.broadcast_to(np.asarray(lens, dtype=np.uint32), (n,))
+    p["mss"] = np.broadcast_to(np.asarray(msss, dtype=np.uint16), (n,))
+    p["dst_offset"] = np.asarray(dst_offsets, dtype=np.uint64)
+    p["cap"] = np.broadcast_to(np.asarray(caps, dtype=np.uint32), (n,))
     return p
 
 
@@ -379,6 +399,32 @@ class ChecksumEngine:
               "smol_csum_batch_fragment_emit")
         return out
 
+    def tcp_segment_emit(self, buf, batch: Batch, src, dst, plans, frame_stride: int = 0, caps=None, out=None, stream=None):
+        """Every send cut into MSS-sized TCP segments at its place in `dst`, every checksum filled, in one
+        pass over the payload (smol_csum_batch_tcp_segment_emit).  Each record of the batch is one header
+        template (Ethernet if any, IP, TCP with options, no payload); `plans`: a device uint8 tensor of one
+        smol_csum_tcpplan_t per record (see make_tcpplans), naming the send's payload range in `src`;
+        `frame_stride`: bytes from one frame of a send to the next (0: back to back); `dst`: the destination
+        uint8 device tensor, written only inside the frames.  Returns an n x 16 uint8 device tensor of
+        smol_csum_tcpout_t (view its host copy as TCPOUT_DTYPE).  `buf` and `src` are only read."""
+        import torch
+
+        self._check_buf(buf, batch)
+        assert src.is_cuda and src.dtype.itemsize == 1 and src.is_contiguous()
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert plans.is_cuda and plans.is_contiguous() and plans.numel() * plans.dtype.itemsize >= 32 * batch.n
+        assert 0 <= int(frame_stride) < 1 << 32
+        if out is None:
+            out = torch.empty((batch.n, 16), dtype=torch.uint8, device=buf.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.dtype.itemsize >= 16 * batch.n
+        b = batch.c()
+        c = _caps(caps)
+        check(self._L.smol_csum_batch_tcp_segment_emit(self._h, buf.data_ptr(), ctypes.byref(b), ctypes.byref(c),
+                                                     src.data_ptr(), dst.data_ptr(), plans.data_ptr(),
+                                                     int(frame_stride), out.data_ptr(), self._stream(stream)),
+              "smol_csum_batch_tcp_segment_emit")
+        return out
+
     def nhc_udp_emit(self, buf, batch: Batch, addrs, caps=None, status=None, stream=None):
         """6LoWPAN NHC UDP emit (smol_csum_batch_nhc_udp_emit): ``addrs`` is a device uint8 tensor of
         n x 32 bytes (IPv6 source, destination per record)."""
@@ -555,13 +601,13 @@ class ChecksumEngine:
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
         "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
-        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel", "variant": VAR, "G":
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
                  6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel",
-                 11: "fragcopy_kernel", 12: "fragcut_kernel"}
+                 11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

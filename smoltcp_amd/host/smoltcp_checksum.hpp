@@ -280,6 +280,19 @@ public:
         check(smol_csum_batch_fragment_emit(ctx_, d_buf, &bc, &cc, d_dst, d_plans, frame_stride, d_out, stream),
               "smol_csum_batch_fragment_emit");
     }
+    // emit, and in the same pass every TCP send cut into MSS-sized segments (the burst of TcpSocket::dispatch
+    // calls within one poll, src/socket/tcp.rs:2620-2687): record i is the header template, d_plans[i] its
+    // payload range in d_src, its MSS and its place in d_dst, frame k at + k * frame_stride (0: back to
+    // back); d_out[i] = the frame count and lengths, emit's status byte and whether the frames were stored.
+    // d_plans / d_out: one per record.  d_buf and d_src are only read.
+    void tcp_segment_emit(const uint8_t* d_buf, const Batch& b, const uint8_t* d_src, uint8_t* d_dst,
+                          const smol_csum_tcpplan_t* d_plans, smol_csum_tcpout_t* d_out, uint32_t frame_stride = 0,
+                          const smoltcp::phy::ChecksumCapabilities& caps = {}, void* stream = nullptr) {
+        auto bc = b.c();
+        auto cc = caps.c();
+        check(smol_csum_batch_tcp_segment_emit(ctx_, d_buf, &bc, &cc, d_src, d_dst, d_plans, frame_stride, d_out, stream),
+              "smol_csum_batch_tcp_segment_emit");
+    }
 
     // 6LoWPAN NHC UDP (sixlowpan::nhc::UdpNhcRepr::emit / ::parse): every record is a LOWPAN_NHC
     // UDP packet; d_addrs[i] holds record i's IPv6 addresses (IPHC-decompressed).
