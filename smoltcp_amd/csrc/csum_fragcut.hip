@@ -11,12 +11,14 @@
 //
 // One wavefront per datagram, four datagrams per 256-thread workgroup; no LDS, no barrier (the frames are
 // regular: frame k's payload is [k step, (k + 1) step), so there is no datagram map to share).
-//   1. Gate.  The wave parses the record with parse_geometry (csum_device.h, the emit flavour): the status
-//      byte, the L4 span and the offsets of the fields emit writes are emit's by construction.  The cut
-//      (count, frame lengths) and the cap / stride test follow; a datagram that is not cut or does not fit
-//      streams nothing.
-//   2. Streaming.  The wave walks the frames in order.  A frame's payload slice is streamed as a
-//      vcopy::Piece (csum_walk.h, fragcopy's streamer), U chunks per lane and step, all loads of a step
+// The record gate, the cap / stride test, the result entry and the launcher are csum_cut.h's, shared with
+// csum_tcpcut.hip.
+//   1. Gate.  The wave parses the record with parse_geometry (cut::gate): the status byte, the L4 span and
+//      the offsets of the fields emit writes are emit's by construction.  The cut rules and the cut (count,
+//      frame lengths: a cut::Cut) are written here, the cap / stride test (cut::place) follows; a datagram
+//      that is not cut or does not fit streams nothing.
+//   2. Streaming.  The wave walks the frames in order (vcopy::piece_walk, csum_walk.h).  A frame's payload
+//      slice is streamed as a vcopy::Piece, cut::U chunks per lane and step, all loads of a step
 //      issued first, and the first step of the NEXT frame is issued before the current one is used.  Each
 //      chunk is summed as aligned words (edges masked, UDP capped at its length field: the tail is
 //      delivered, not summed) and funnelled onto the destination's 16-B grid.  The shift is per frame: the
@@ -31,22 +33,15 @@
 //      nothing depends on the order of two stores.  step is a multiple of 8 and the offsets are even, so
 //      a field never straddles two frames.
 // No byte of d_dst is read.
-#include "csum_fraggroup.h"
+#include "csum_cut.h"
 
 namespace smolcsum {
 namespace fragcut {
 
-using fraggroup::rb;
-using fraggroup::rb16;
-
-constexpr int U = 2;  // chunks per lane and step: a 1480-B slice is one step
-constexpr uint32_t STEP = 64 * U;
 constexpr int32_t NO_HOLD = -(1 << 30);
 
-// One frame: its payload slice (the same for every lane of the wave) and what the frame head needs.
-struct Frame {
-    vcopy::Piece<false> q;  // the slice: all of it delivered, its bytes below the L4 span's end summed
-    uint64_t F;      // destination address of the frame's first byte
+// One frame: its payload slice (its bytes below the L4 span's end summed) and what the frame head needs.
+struct Frame : cut::Frame {
     uint32_t lo;     // datagram-payload offset of the slice
     int32_t h0, h1;  // slice-relative offsets of the held-back fields (far below 0: none)
     uint32_t more;   // another frame follows (MF)
@@ -75,36 +70,36 @@ __global__ __launch_bounds__(256) void fragcut_kernel(KParams p, FragCutArgs v) 
 
     for (uint64_t r = 4ull * blockIdx.x + wave; r < p.n; r += nwaves) {
         // ---- 1. the gate: emit's parse, the cut, the cap ----
-        const RecRef rr = rec_at<IMPLICIT, false>(p, r);
-        const uint64_t a0 = rr.a0;
-        auto rd = [&](uint32_t o) -> uint32_t { return rb(a0 + o); };
-        const Geom g = parse_geometry<false>(rd, rr.len, rr.kind, true);
+        const cut::Gate gt = cut::gate<IMPLICIT>(p, r);
+        const cut::Rd rd = gt.rd;
+        const uint64_t a0 = rd.a0;
+        const Geom g = gt.g;
         const u32x4 pl = *(gcv4)((uint64_t)v.plans + 16ull * r);  // dst_offset, cap, ip_mtu | ident << 16
         const uint32_t cap = pl.z, mtu = pl.w & 0xffffu, ident = pl.w >> 16;
         const uint32_t io = g.ip_off, l4o = io + 20;
         const uint64_t ip = a0 + io;
         // cut: an IPv4 header that passed check_len (fam 4), IHL 5, not itself a fragment, ip_mtu >= 28
-        bool cut = g.fam == 4 && g.ip_hl == 20 && mtu >= 28;
+        bool is_cut = g.fam == 4 && g.ip_hl == 20 && mtu >= 28;
         uint32_t total = 20, id0 = 0, fl0 = 0;
-        if (cut) {
+        if (is_cut) {
             total = rb16(ip + 2);
             id0 = rb16(ip + 4);
             fl0 = rb16(ip + 6);
-            cut = (fl0 & 0x3fffu) == 0;
+            is_cut = (fl0 & 0x3fffu) == 0;
         }
         const uint32_t T = total - 20;
         const uint32_t step = (mtu - 20) & ~7u;  // max_ipv4_fragment_size, phy/mod.rs:297-300
         const bool single = 20 + T <= mtu;        // the iface sends it as it is, mod.rs:1276
-        uint32_t count = 0, frame_len = 0, last_len = 0;
-        if (cut) {
-            count = single ? 1u : (T + step - 1) / step;
-            frame_len = single ? l4o + T : l4o + step;
-            last_len = l4o + T - (count - 1) * (single ? 0u : step);
+        cut::Cut ct = {0u, 0u, 0u};
+        if (is_cut) {
+            ct.count = single ? 1u : (T + step - 1) / step;
+            ct.frame_len = single ? l4o + T : l4o + step;
+            ct.last_len = l4o + T - (ct.count - 1) * (single ? 0u : step);
         }
-        const uint32_t S = v.frame_stride ? v.frame_stride : frame_len;
-        const bool fits = cut && (uint64_t)(count - 1) * S + last_len <= cap && S >= frame_len;  // before the first store
+        const cut::Place at = cut::place(ct, v.frame_stride, cap);  // before the first store
+        const uint32_t count = ct.count, S = at.S;
 
-        if (fits) {
+        if (at.fits) {
             const bool l4 = g.proto != P_NONE && !(g.st & SMOL_ST_MALFORMED);
             const uint32_t span = l4 ? g.span_end - l4o : 0u;  // payload bytes summed
             const int32_t f1 = l4 ? (int32_t)g.fo : NO_HOLD;
@@ -139,30 +134,10 @@ __global__ __launch_bounds__(256) void fragcut_kernel(KParams p, FragCutArgs v) 
             };
 
             uint32_t acc = 0;  // this lane's part of the aligned-word sum over the summed payload bytes
-            {
-                Frame cur = setup(0u);
-                u32x4 c[U], xh;
-                vcopy::piece_load<U>(cur.q, 0u, lane, dummy, c, xh);
-                for (uint32_t k = 0; k < count; ++k) {
-                    Frame nxt = {};
-                    u32x4 cn[U], xn;
-                    if (k + 1 < count) {  // the next frame's first step, in flight under this one's work
-                        nxt = setup(k + 1);
-                        vcopy::piece_load<U>(nxt.q, 0u, lane, dummy, cn, xn);
-                    }
-                    head(cur);
-                    const HeldBack hold = {cur.h0, cur.h1};
-                    vcopy::piece_use<U>(cur.q, 0u, lane, c, xh, acc, hold);
-                    for (uint32_t i0 = STEP; i0 < cur.q.nk; i0 += STEP) {
-                        vcopy::piece_load<U>(cur.q, i0, lane, dummy, c, xh);
-                        vcopy::piece_use<U>(cur.q, i0, lane, c, xh, acc, hold);
-                    }
-                    cur = nxt;
-#pragma unroll
-                    for (int u = 0; u < U; ++u) c[u] = cn[u];
-                    xh = xn;
-                }
-            }
+            vcopy::piece_walk<cut::U>(count, lane, dummy, setup, cut::SliceOf{}, [&](const Frame& f, uint32_t, auto stream) {
+                head(f);
+                stream(acc, HeldBack{f.h0, f.h1});
+            });
 
             // ---- 4. emit's finish over the sums, and the held-back fields ----
             if (l4) {
@@ -188,21 +163,14 @@ __global__ __launch_bounds__(256) void fragcut_kernel(KParams p, FragCutArgs v) 
                 }
             }
         }
-        if (lane == 0) {  // smol_csum_fragout_t: count, frame_len, last_len, status | written << 8
-            const u32x4 o = {count, frame_len, last_len, (g.st & 0xffu) | (fits ? 0x100u : 0u)};
-            *(GMEM u32x4*)((uint64_t)v.out + 16ull * r) = o;
-        }
+        cut::store_result(v.out, r, lane, ct, g.st, at.fits);
     }
 }
 
 }  // namespace fragcut
 
 hipError_t launch_fragcut(const KParams& p, const FragCutArgs& v, hipStream_t s) {
-    const uint32_t blocks = grid_blocks((p.n + 3) / 4, kMaxGridBlocks);
-    note_launch(KERN_FRAGCUT, 0, 64, fragcut::U);
-    if (p.desc == nullptr) hipLaunchKernelGGL((fragcut::fragcut_kernel<true>), dim3(blocks), dim3(256), 0, s, p, v);
-    else hipLaunchKernelGGL((fragcut::fragcut_kernel<false>), dim3(blocks), dim3(256), 0, s, p, v);
-    return hipGetLastError();
+    return cut::launch(KERN_FRAGCUT, fragcut::fragcut_kernel<true>, fragcut::fragcut_kernel<false>, p, v, s);
 }
 
 }  // namespace smolcsum

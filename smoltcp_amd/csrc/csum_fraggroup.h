@@ -31,9 +31,6 @@ namespace fraggroup {
 
 constexpr uint32_t MAXF = SMOL_MAX_FRAGMENTS;
 
-__device__ __forceinline__ uint32_t rb(uint64_t a) { return *(gcu8)a; }
-__device__ __forceinline__ uint32_t rb16(uint64_t a) { return (rb(a) << 8) | rb(a + 1); }
-
 __device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
 #pragma unroll
     for (int m = 32; m; m >>= 1) v += (uint32_t)__shfl_xor((int)v, m, 64);

@@ -11,21 +11,22 @@
 // (src/wire/ipv4.rs:584-611) or Ipv6Repr::emit (src/wire/ipv6.rs:628-640).  Here every 16-B chunk of the
 // payload is loaded once: the registers are summed and the same registers feed the stores.
 //
-// One wavefront per send, four sends per 256-thread workgroup; no LDS, no barrier.
-//   1. Gate.  The wave parses the template with parse_geometry (csum_device.h, the emit flavour): the
-//      status byte is emit's by construction.  The cut rules of the header (TCP straight behind a plain IP
-//      header, no payload of its own, SYN and RST clear, mss >= 1, the IP length field fits), the cut
-//      (count, frame lengths) and the cap / stride test follow; a send that is not cut or does not fit
-//      streams nothing and stores nothing.
+// One wavefront per send, four sends per 256-thread workgroup; no LDS, no barrier.  The record gate, the
+// cap / stride test, the result entry and the launcher are csum_cut.h's, shared with csum_fragcut.hip.
+//   1. Gate.  The wave parses the template with parse_geometry (cut::gate): the status byte is emit's by
+//      construction.  The cut rules of the header (TCP straight behind a plain IP header, no payload of
+//      its own, SYN and RST clear, mss >= 1, the IP length field fits) and the cut (count, frame lengths:
+//      a cut::Cut) are written here, the cap / stride test (cut::place) follows; a send that is not cut
+//      or does not fit streams nothing and stores nothing.
 //   2. Once per send.  Lane i < hl / 2 holds big-endian word i of the head (hl is even: io is 0 or 14, the
 //      headers are multiples of 4).  Two wave reductions over those lanes give what no frame changes: the
 //      TCP sum's constant part (the pseudo-header's addresses and protocol, every TCP header word but the
 //      sequence number, the flags word and the checksum) and the IPv4 header's (every word but total
 //      length and checksum).
-//   3. Per frame.  The payload slice is streamed as a vcopy::Piece (csum_walk.h, fragcopy's and fragcut's
-//      streamer), U chunks per lane and step, all loads of a step issued first, and the first step of the
-//      NEXT frame is issued before the current one is used.  Nothing is held back (vcopy::NoHold): the
-//      checksum field lies in the head, not in the stream.  The frame's payload sum is its own: it is
+//   3. Per frame (vcopy::piece_walk, csum_walk.h: fragcopy's and fragcut's pipeline).  The payload slice is
+//      streamed as a vcopy::Piece, cut::U chunks per lane and step, all loads of a step issued first, and
+//      the first step of the NEXT frame is issued before the current one is used.  Nothing is held back
+//      (vcopy::NoHold): the checksum field lies in the head, not in the stream.  The frame's payload sum is its own: it is
 //      reduced across the wave once the slice is streamed; the lanes sum aligned little-endian words, so
 //      for a slice at an even source address the folded sum is byte-swapped into the header's big-endian
 //      words, at an odd one it already is (RFC 1071 2(B)) -- an odd mss makes every second slice odd.
@@ -33,26 +34,16 @@
 //      flags word and the lengths, substitutes its word if it is one of the rewritten ones, and stores it
 //      (one 2-byte store per lane where the frame starts even, two byte stores where it starts odd: the
 //      lanes' stores are consecutive either way).
-//   4. Result.  Lane 0 writes the 16-byte entry, also for a send that is not cut.
+//   4. Result.  Lane 0 writes the 16-byte entry (cut::store_result), also for a send that is not cut.
 // Stores and cache policy are fragcut's: plain loads and stores, dwordx4 inside a slice, byte-masked edges,
 // nothing read back from d_dst.  The one departure: the head goes out after its frame's slice, not
 // before, because it carries the frame's own checksum.
-#include "csum_fraggroup.h"
+#include "csum_cut.h"
 
 namespace smolcsum {
 namespace tcpcut {
 
-using fraggroup::rb;
-using fraggroup::rb16;
-
-constexpr int U = 2;  // chunks per lane and step: a 1460-B slice is one step
-constexpr uint32_t STEP = 64 * U;
-
-// One frame: its payload slice (the same for every lane of the wave) and where the frame starts.
-struct Frame {
-    vcopy::Piece<false> q;  // the slice: all of it summed and delivered
-    uint64_t F;             // destination address of the frame's first byte
-};
+using cut::Frame;  // (all of the slice is summed)
 
 template <bool IMPLICIT>
 __global__ __launch_bounds__(256) void tcpcut_kernel(KParams p, TcpCutArgs v) {
@@ -63,10 +54,9 @@ __global__ __launch_bounds__(256) void tcpcut_kernel(KParams p, TcpCutArgs v) {
 
     for (uint64_t r = 4ull * blockIdx.x + wave; r < p.n; r += nwaves) {
         // ---- 1. the gate: emit's parse, the cut rules, the cut, the cap ----
-        const RecRef rr = rec_at<IMPLICIT, false>(p, r);
-        const uint64_t a0 = rr.a0;
-        auto rd = [&](uint32_t o) -> uint32_t { return rb(a0 + o); };
-        const Geom g = parse_geometry<false>(rd, rr.len, rr.kind, true);
+        const cut::Gate gt = cut::gate<IMPLICIT>(p, r);
+        const uint64_t a0 = gt.rd.a0;
+        const Geom g = gt.g;
         const u32x4 pa = *(gcv4)((uint64_t)v.plans + 32ull * r);       // src_offset, len, mss | reserved << 16
         const u32x4 pb = *(gcv4)((uint64_t)v.plans + 32ull * r + 16);  // dst_offset, cap, reserved2
         const uint32_t len = pa.z, mss = pa.w & 0xffffu, cap = pb.z;
@@ -74,29 +64,29 @@ __global__ __launch_bounds__(256) void tcpcut_kernel(KParams p, TcpCutArgs v) {
         const uint64_t tcp = a0 + l4o;
         // cut: a TCP header that passed check_len straight behind an IPv4 header of IHL 5 or an IPv6 header
         // (no Hop-by-Hop header), nothing behind it, SYN and RST clear, and an IP length field that fits
-        bool cut = g.st == 0 && g.proto == P_TCP && mss >= 1 &&
-                   ((g.fam == 4 && g.ip_hl == 20) || (g.fam == 6 && l4o == io + 40));
+        bool is_cut = g.st == 0 && g.proto == P_TCP && mss >= 1 &&
+                      ((g.fam == 4 && g.ip_hl == 20) || (g.fam == 6 && l4o == io + 40));
         uint32_t thl = 20, seq0 = 0, fl0 = 0;
-        if (cut) {
+        if (is_cut) {
             fl0 = rb16(tcp + 12);
             thl = (fl0 >> 12) * 4;
             seq0 = (rb16(tcp + 4) << 16) | rb16(tcp + 6);
-            cut = g.l4_len == thl && (fl0 & 0x06u) == 0;
+            is_cut = g.l4_len == thl && (fl0 & 0x06u) == 0;
         }
         const uint32_t p0 = min(mss, len);  // payload bytes of every frame but the last
         const uint32_t iplen0 = (g.fam == 4 ? 20u : 0u) + thl;  // the IP length field of a bare segment
-        cut = cut && iplen0 + p0 <= 65535u;
+        is_cut = is_cut && iplen0 + p0 <= 65535u;
         const uint32_t hl = l4o + thl;
-        uint32_t count = 0, frame_len = 0, last_len = 0;
-        if (cut) {
-            count = len ? (uint32_t)(((uint64_t)len + mss - 1) / mss) : 1u;
-            frame_len = hl + p0;
-            last_len = hl + (len - (count - 1) * mss);
+        cut::Cut ct = {0u, 0u, 0u};
+        if (is_cut) {
+            ct.count = len ? (uint32_t)(((uint64_t)len + mss - 1) / mss) : 1u;
+            ct.frame_len = hl + p0;
+            ct.last_len = hl + (len - (ct.count - 1) * mss);
         }
-        const uint32_t S = v.frame_stride ? v.frame_stride : frame_len;
-        const bool fits = cut && (uint64_t)(count - 1) * S + last_len <= cap && S >= frame_len;  // before the first store
+        const cut::Place at = cut::place(ct, v.frame_stride, cap);  // before the first store
+        const uint32_t count = ct.count, S = at.S;
 
-        if (fits) {
+        if (at.fits) {
             const uint64_t Sbase = (uint64_t)v.src + ((uint64_t)pa.x | ((uint64_t)pa.y << 32));
             const uint64_t Dbase = (uint64_t)v.dst + ((uint64_t)pb.x | ((uint64_t)pb.y << 32));
             // ---- 2. the head: this lane's word of the template, and what no frame changes ----
@@ -135,47 +125,22 @@ __global__ __launch_bounds__(256) void tcpcut_kernel(KParams p, TcpCutArgs v) {
                 if (mine) store_be16((gu8)(f.F + 2u * (uint32_t)lane), w);
             };
 
-            Frame cur = setup(0u);
-            u32x4 c[U], xh;
-            vcopy::piece_load<U>(cur.q, 0u, lane, dummy, c, xh);
-            for (uint32_t k = 0; k < count; ++k) {
-                Frame nxt = {};
-                u32x4 cn[U], xn;
-                if (k + 1 < count) {  // the next frame's first step, in flight under this one's work
-                    nxt = setup(k + 1);
-                    vcopy::piece_load<U>(nxt.q, 0u, lane, dummy, cn, xn);
-                }
+            vcopy::piece_walk<cut::U>(count, lane, dummy, setup, cut::SliceOf{}, [&](const Frame& f, uint32_t k, auto stream) {
                 uint32_t acc = 0;  // this lane's part of the aligned-word sum over the frame's payload
-                const vcopy::NoHold hold = {};
-                vcopy::piece_use<U>(cur.q, 0u, lane, c, xh, acc, hold);
-                for (uint32_t i0 = STEP; i0 < cur.q.nk; i0 += STEP) {
-                    vcopy::piece_load<U>(cur.q, i0, lane, dummy, c, xh);
-                    vcopy::piece_use<U>(cur.q, i0, lane, c, xh, acc, hold);
-                }
+                stream(acc, vcopy::NoHold{});
                 // (a lane sums at most 65 chunks of a 65535-B slice: no wrap; folded before the wave's sum)
                 const uint32_t le = fold32(group_sum<64>(fold32(acc)));
-                head(cur, k, cur.q.odd() ? le : bswap16(le));
-                cur = nxt;
-#pragma unroll
-                for (int u = 0; u < U; ++u) c[u] = cn[u];
-                xh = xn;
-            }
+                head(f, k, f.q.odd() ? le : bswap16(le));
+            });
         }
-        if (lane == 0) {  // smol_csum_tcpout_t: count, frame_len, last_len, status | written << 8
-            const u32x4 o = {count, frame_len, last_len, (g.st & 0xffu) | (fits ? 0x100u : 0u)};
-            *(GMEM u32x4*)((uint64_t)v.out + 16ull * r) = o;
-        }
+        cut::store_result(v.out, r, lane, ct, g.st, at.fits);
     }
 }
 
 }  // namespace tcpcut
 
 hipError_t launch_tcpcut(const KParams& p, const TcpCutArgs& v, hipStream_t s) {
-    const uint32_t blocks = grid_blocks((p.n + 3) / 4, kMaxGridBlocks);
-    note_launch(KERN_TCPCUT, 0, 64, tcpcut::U);
-    if (p.desc == nullptr) hipLaunchKernelGGL((tcpcut::tcpcut_kernel<true>), dim3(blocks), dim3(256), 0, s, p, v);
-    else hipLaunchKernelGGL((tcpcut::tcpcut_kernel<false>), dim3(blocks), dim3(256), 0, s, p, v);
-    return hipGetLastError();
+    return cut::launch(KERN_TCPCUT, tcpcut::tcpcut_kernel<true>, tcpcut::tcpcut_kernel<false>, p, v, s);
 }
 
 }  // namespace smolcsum

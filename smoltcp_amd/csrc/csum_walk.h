@@ -96,6 +96,11 @@ typedef const GMEM uint8_t* gcu8;
 typedef GMEM uint8_t* gu8;
 typedef GMEM uint16_t* gu16;
 
+// One byte / one big-endian u16 at an absolute device address (the header reads of the fragment-group
+// and cut kernels).
+__device__ __forceinline__ uint32_t rb(uint64_t a) { return *(gcu8)a; }
+__device__ __forceinline__ uint32_t rb16(uint64_t a) { return (rb(a) << 8) | rb(a + 1); }
+
 struct RecRef {
     uint64_t a0;  // absolute address of the record's first byte
     uint32_t len;
@@ -442,7 +447,8 @@ __device__ __forceinline__ void store_part(gu8 dst, const u32x4& c, int lo, int 
 }
 
 // The sum-and-deliver kernels' chunk helpers (csum_vcopy.hip; sum_chunk is above) and, for the kernels that
-// stream one piece after the other with a whole wave (csum_fragcopy.hip, csum_fragcut.hip), the piece streamer.
+// stream one piece after the other with a whole wave (csum_fragcopy.hip, csum_fragcut.hip, csum_tcpcut.hip),
+// the piece streamer and, for the cut kernels, its pipeline (piece_walk).
 namespace vcopy {
 
 // The chunk the next lane of the group holds (lane G - 1: lane 0's).
@@ -507,15 +513,20 @@ struct Piece {
 
 // The loads of one step, U chunks per lane: chunk slots [i0, i0 + 64 U), and for lane 63 the slot after
 // them (xh).  All of them issued unconditionally; what does not exist reads the dummy line.
+// xh is issued FIRST.  Loads return in issue order and a wait names how many of the youngest may still be
+// out, so with xh last the wait in front of the exchange was vmcnt(0): it drained every load behind it too.
+// (The compiler had this order in the cut kernels' first loops and lost it when text around them changed.)
+// fragment_emit / tcp_segment_emit with xh last against first, interleaved on one MI355X: 0.1480 / 0.1366
+// and 0.6161 / 0.5352 ms (64 KB records), 0.1078 / 0.1024 and 0.3522 / 0.3126 ms (8 KB).
 template <int U, bool SO>
 __device__ __forceinline__ void piece_load(const Piece<SO>& q, uint32_t i0, int lane, uint64_t dummy, u32x4 (&c)[U], u32x4& xh) {
+    const uint32_t kx = i0 + 64u * U - q.lead;
+    xh = ld16<false>((gcv4)(q.delivers() && lane == 63 && kx < q.nch ? q.base + 16ull * kx : dummy));
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const uint32_t k = i0 + (uint32_t)(u * 64 + lane) - q.lead;  // (slot 0 of a lead: wraps, >= nch)
         c[u] = ld16<false>((gcv4)(k < q.nch ? q.base + 16ull * k : dummy));
     }
-    const uint32_t kx = i0 + 64u * U - q.lead;
-    xh = ld16<false>((gcv4)(q.delivers() && lane == 63 && kx < q.nch ? q.base + 16ull * kx : dummy));
 }
 
 // Nothing of a destination chunk is held back.
@@ -555,6 +566,43 @@ __device__ __forceinline__ void piece_use(const Piece<SO>& q, uint32_t i0, int l
                 else store_edge(dst, m, lo, end);
             }
         }
+    }
+}
+
+// The piece pipeline of a wave: items 0 .. count - 1, one after the other, each item's first
+// step issued before the item in front of it is used, so a lane has up to 2 U chunks (and the two
+// successor chunks) in flight.  setup(j) makes item j, piece(item) is its Piece (an item may carry more:
+// the cut kernels' frames), and body(item, j, stream) does the kernel's own work around the call
+// stream(acc, hold), which sums the piece into acc and delivers it (piece_use) step by step.
+// fragcopy_kernel keeps its own loop of this shape (fragments wave, wave + 4, ...): on this one its
+// 45-fragment groups took 0.1220 ms against 0.1158 (verify_reassemble, 2^11 x 65,515 B, interleaved on
+// one MI355X).
+template <int U, class SETUP, class PIECE, class BODY>
+__device__ __forceinline__ void piece_walk(uint32_t count, int lane, uint64_t dummy, const SETUP& setup, const PIECE& piece,
+                                           const BODY& body) {
+    if (count == 0) return;
+    auto cur = setup(0u);
+    u32x4 c[U], xh;
+    piece_load<U>(piece(cur), 0u, lane, dummy, c, xh);
+    for (uint32_t j = 0; j < count; ++j) {
+        decltype(cur) nxt = {};
+        u32x4 cn[U], xn;
+        if (j + 1 < count) {  // the next item's first step, in flight under this one's work
+            nxt = setup(j + 1);
+            piece_load<U>(piece(nxt), 0u, lane, dummy, cn, xn);
+        }
+        body(cur, j, [&](uint32_t& acc, const auto& hold) {
+            const auto& q = piece(cur);
+            piece_use<U>(q, 0u, lane, c, xh, acc, hold);
+            for (uint32_t i0 = 64u * U; i0 < q.nk; i0 += 64u * U) {
+                piece_load<U>(q, i0, lane, dummy, c, xh);
+                piece_use<U>(q, i0, lane, c, xh, acc, hold);
+            }
+        });
+        cur = nxt;
+#pragma unroll
+        for (int u = 0; u < U; ++u) c[u] = cn[u];
+        xh = xn;
     }
 }
 

@@ -375,6 +375,20 @@ class ChecksumEngine:
               "smol_csum_batch_verify_reassemble")
         return status, dgrams
 
+    def _check_cut(self, buf, batch: Batch, dst, plans, plan_bytes: int, frame_stride: int, out):
+        """The argument checks fragment_emit and tcp_segment_emit share (batch buffer, destination, one
+        plan_bytes plan per record, frame stride, result entries); returns `out`, a fresh n x 16 tensor if None."""
+        import torch
+
+        self._check_buf(buf, batch)
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert plans.is_cuda and plans.is_contiguous() and plans.numel() * plans.dtype.itemsize >= plan_bytes * batch.n
+        assert 0 <= int(frame_stride) < 1 << 32
+        if out is None:
+            out = torch.empty((batch.n, 16), dtype=torch.uint8, device=buf.device)
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.dtype.itemsize >= 16 * batch.n
+        return out
+
     def fragment_emit(self, buf, batch: Batch, dst, plans, frame_stride: int = 0, caps=None, out=None, stream=None):
         """Emit, and in the same pass every whole IPv4 datagram of the batch cut into the frames the iface
         sends, at its place in `dst` (smol_csum_batch_fragment_emit).  `plans`: a device uint8 tensor of one
@@ -382,15 +396,7 @@ class ChecksumEngine:
         datagram to the next (0: back to back); `dst`: the destination uint8 device tensor, written only
         inside the frames.  Returns an n x 16 uint8 device tensor of smol_csum_fragout_t (view its host copy
         as FRAGOUT_DTYPE).  `buf` is only read."""
-        import torch
-
-        self._check_buf(buf, batch)
-        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
-        assert plans.is_cuda and plans.is_contiguous() and plans.numel() * plans.dtype.itemsize >= 16 * batch.n
-        assert 0 <= int(frame_stride) < 1 << 32
-        if out is None:
-            out = torch.empty((batch.n, 16), dtype=torch.uint8, device=buf.device)
-        assert out.is_cuda and out.is_contiguous() and out.numel() * out.dtype.itemsize >= 16 * batch.n
+        out = self._check_cut(buf, batch, dst, plans, 16, frame_stride, out)
         b = batch.c()
         c = _caps(caps)
         check(self._L.smol_csum_batch_fragment_emit(self._h, buf.data_ptr(), ctypes.byref(b), ctypes.byref(c),
@@ -407,16 +413,8 @@ class ChecksumEngine:
         `frame_stride`: bytes from one frame of a send to the next (0: back to back); `dst`: the destination
         uint8 device tensor, written only inside the frames.  Returns an n x 16 uint8 device tensor of
         smol_csum_tcpout_t (view its host copy as TCPOUT_DTYPE).  `buf` and `src` are only read."""
-        import torch
-
-        self._check_buf(buf, batch)
         assert src.is_cuda and src.dtype.itemsize == 1 and src.is_contiguous()
-        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
-        assert plans.is_cuda and plans.is_contiguous() and plans.numel() * plans.dtype.itemsize >= 32 * batch.n
-        assert 0 <= int(frame_stride) < 1 << 32
-        if out is None:
-            out = torch.empty((batch.n, 16), dtype=torch.uint8, device=buf.device)
-        assert out.is_cuda and out.is_contiguous() and out.numel() * out.dtype.itemsize >= 16 * batch.n
+        out = self._check_cut(buf, batch, dst, plans, 32, frame_stride, out)
         b = batch.c()
         c = _caps(caps)
         check(self._L.smol_csum_batch_tcp_segment_emit(self._h, buf.data_ptr(), ctypes.byref(b), ctypes.byref(c),

@@ -4,24 +4,21 @@ From the header templates, the plans, the payload source, the frame stride and t
 smol_csum_tcpout_t array and the destination arena, which starts as a sentinel fill so that a stray store
 or a missing byte shows.  Per record: oracle.batch_emit on a copy of the template (the status byte), the
 header's eligibility rules, then per frame the rewritten headers and the payload slice put together here
-and oracle.batch_emit on that frame (every checksum), then the cap and stride rules.  Nothing here computes
-a checksum of its own.
+and oracle.batch_emit on that frame (every checksum); the cap and stride rules and the arena are
+tests/cut_ref.py's.  Nothing here computes a checksum of its own.
 """
 from __future__ import annotations
 
 import numpy as np
 
-import oracle
+from tests.cut_ref import OUT_DTYPE as TCPOUT_DTYPE
+from tests.cut_ref import SENTINEL, emit_record, new_results, place  # noqa: F401  (re-exported)
 
 KIND_IP, KIND_ETH = 1, 2
 REC_IPHDR_ONLY = 0x01
-SENTINEL = 0xA5
 
 TCPPLAN_DTYPE = np.dtype([("src_offset", "<u8"), ("len", "<u4"), ("mss", "<u2"), ("reserved", "<u2"), ("dst_offset", "<u8"),
                           ("cap", "<u4"), ("reserved2", "<u4")])
-TCPOUT_DTYPE = np.dtype([("count", "<u4"), ("frame_len", "<u4"), ("last_len", "<u4"), ("status", "u1"), ("written", "u1"),
-                         ("reserved", "<u2")])
-
 
 A4, B4 = bytes([10, 0, 0, 1]), bytes([10, 0, 0, 2])
 A6, B6 = bytes(range(0x20, 0x30)), bytes(range(0x40, 0x50))
@@ -80,15 +77,6 @@ def not_cut_cases(rng):
         ("overflow", template(rng, doff=15), KIND_IP, 0, 65535, 65535),
         ("overflow6", template(rng, v6=True, doff=6), KIND_IP, 0, 65535, 65520),
     ]
-
-
-def emit_record(rec: bytes, kind: int, flags: int, caps):
-    """(status byte, record bytes) after smol_csum_batch_emit's oracle on a copy of the record."""
-    a = np.frombuffer(rec, np.uint8).copy()
-    if a.size == 0:
-        return int(oracle.batch_emit(np.zeros(1, np.uint8), None, 1, 0, 0, oracle.kind_flags(kind, flags), caps)[0]), b""
-    st = oracle.batch_emit(a, None, 1, a.size, a.size, oracle.kind_flags(kind, flags), caps)
-    return int(st[0]), a.tobytes()
 
 
 def template_geometry(rec: bytes, kind: int, flags: int):
@@ -161,29 +149,12 @@ def frames_of(rec: bytes, kind: int, flags: int, payload: bytes, mss: int, caps)
 def expected(recs, kinds, flags, plans, src, frame_stride: int, caps, arena_size: int, sentinel: int = SENTINEL):
     """recs: the templates as they stand in the batch (bytes each); kinds / flags: one per record; plans: a
     TCPPLAN_DTYPE array, one per record; src: the payload source (uint8 array).  Returns (out entries, arena)."""
-    n = len(recs)
-    out = np.zeros(n, TCPOUT_DTYPE)
-    arena = np.full(arena_size, sentinel, np.uint8)
-    for i in range(n):
-        pl = plans[i]
+    out, arena = new_results(len(recs), arena_size, sentinel)
+    for i, pl in enumerate(plans):
         so, ln = int(pl["src_offset"]), int(pl["len"])
-        st, _ = emit_record(recs[i], int(kinds[i]), int(flags[i]), caps)
-        out[i]["status"] = st
-        if so + ln > len(src):  # (a plan of a record that is not cut may name anything)
-            assert frames_of(recs[i], int(kinds[i]), int(flags[i]), b"", int(pl["mss"]), caps)[1] is None
-            continue
-        st, frames = frames_of(recs[i], int(kinds[i]), int(flags[i]), bytes(src[so:so + ln]), int(pl["mss"]), caps)
-        if frames is None:
-            continue
-        count, frame_len, last_len = len(frames), len(frames[0]), len(frames[-1])
-        assert all(len(f) == frame_len for f in frames[:-1])
-        out[i]["count"], out[i]["frame_len"], out[i]["last_len"] = count, frame_len, last_len
-        S = frame_stride or frame_len
-        if (count - 1) * S + last_len > int(pl["cap"]) or (frame_stride and frame_stride < frame_len):
-            continue
-        out[i]["written"] = 1
-        o = int(pl["dst_offset"])
-        for k, f in enumerate(frames):
-            assert o + k * S + len(f) <= arena_size
-            arena[o + k * S:o + k * S + len(f)] = np.frombuffer(f, np.uint8)
+        # (a plan of a record that is not cut may name anything: it is cut as if it named nothing)
+        payload = bytes(src[so:so + ln]) if so + ln <= len(src) else b""
+        st, frames = frames_of(recs[i], int(kinds[i]), int(flags[i]), payload, int(pl["mss"]), caps)
+        assert so + ln <= len(src) or frames is None
+        place(out, arena, i, st, frames, pl, frame_stride)
     return out, arena

@@ -11,6 +11,7 @@ and checks that the launch recorded is fragcut_kernel.
 import numpy as np
 import pytest
 
+from tests import cut_ref as R
 from tests import fragment_ref as C
 from tests import pktgen as P
 from tests import test_frag_cpu as F
@@ -69,46 +70,14 @@ def _run(eng, recs, kind=E.KIND_IP, flags=0, mtu=576, idents=None, stride=0, cap
     flags_a = np.broadcast_to(np.asarray(flags, np.uint8), (n,)).copy()
     mtus = np.broadcast_to(np.asarray(mtu, np.uint16), (n,)).copy()
     idents = 0x4000 + np.arange(n) if idents is None else idents
-    if fixed is not None:
-        rstride, base = fixed
-        buf = np.random.default_rng(seed).integers(0, 256, base + n * rstride + 64, dtype=np.uint8)
-        offs = base + np.arange(n, dtype=np.uint64) * rstride
-        for o, r in zip(offs, recs):
-            assert len(r) <= rstride
-            buf[int(o):int(o) + len(r)] = np.frombuffer(r, np.uint8)
-        lens = np.full(n, rstride, np.uint32)
-        assert (kinds == kinds[0]).all() and (flags_a == flags_a[0]).all()
-    else:
-        buf, offs, lens = P.pack(recs, gap_rng=np.random.default_rng(seed))
-    placed = [bytes(buf[int(o):int(o) + int(ln)]) for o, ln in zip(offs, lens)]
-    # a first pass of the helper with caps of 0 reports what every datagram needs
-    size = C.expected(placed, kinds, flags_a, E.make_fragplans(np.zeros(n), 0, mtus, idents), stride, caps, 1)[0]
-    need = np.where(size["count"] > 0, (size["count"].astype(np.int64) - 1) *
-                    np.where(stride, stride, size["frame_len"]).astype(np.int64) + size["last_len"], 0)
-    slot = np.concatenate([[start], start + np.cumsum(need)]).astype(np.int64)
-    arena_size = int(slot[-1]) + 21
-    plans = E.make_fragplans(slot[:-1], np.maximum(need + cap_adj, 0), mtus, idents)
-    ref_out, ref_arena = C.expected(placed, kinds, flags_a, plans, stride, caps, arena_size)
-
-    if fixed is not None:
-        batch = E.Batch.fixed(n, fixed[0], fixed[0], int(kinds[0]), flags=int(flags_a[0]))
-    else:
-        batch = E.Batch.from_records(offs, lens, kinds, "cuda:0", flags=flags_a)
-    d = torch.from_numpy(buf.copy()).cuda()
-    dv = d[fixed[1]:] if fixed is not None else d
-    dst = torch.full((arena_size,), C.SENTINEL, dtype=torch.uint8, device="cuda")
-    pd = torch.from_numpy(plans.view(np.uint8).copy()).cuda()
+    buf, offs, lens, placed = R.place_records(recs, kinds, flags_a, fixed, np.random.default_rng(seed))
+    plans, slots, ref_out, ref_arena = R.plan_slots(
+        n, lambda o, c: E.make_fragplans(o, c, mtus, idents),
+        lambda pl, size: C.expected(placed, kinds, flags_a, pl, stride, caps, size), stride, start, cap_adj)
+    batch, d, dv, dst, pd = R.upload(E, buf, offs, lens, kinds, flags_a, fixed, plans, ref_arena.size)
     out = eng.fragment_emit(dv, batch, dst, pd, frame_stride=stride, caps=caps)
-    launched = eng.last_launch()
-    got_out = out.cpu().numpy().reshape(-1).view(E.FRAGOUT_DTYPE)
-    got_dst = dst.cpu().numpy()
-    assert launched["kernel"] == "fragcut_kernel", launched
-    assert np.array_equal(d.cpu().numpy(), buf), "the batch buffer is only read"
-    bad = np.nonzero(got_out != ref_out)[0]
-    assert bad.size == 0, f"entries differ at {bad[:8]}: got {got_out[bad[:4]]} want {ref_out[bad[:4]]}"
-    diff = np.nonzero(got_dst != ref_arena)[0]
-    assert diff.size == 0, f"destination bytes differ at {diff[:8]} (got {got_dst[diff[:8]]} want {ref_arena[diff[:8]]})"
-    return got_out, got_dst, slot[:-1]
+    got_out, got_dst = R.compare(eng, "fragcut_kernel", out, dst, ref_out, ref_arena, [(d, buf, "the batch buffer")])
+    return got_out, got_dst, slots
 
 
 # ---- 1. the size sweep ---------------------------------------------------------------------------

@@ -370,6 +370,15 @@ def test_extremes_share_a_launch(eng):
     assert [c for _, c in groups[3:6]] == [256, 65, 45]
 
 
+def test_second_piece_after_a_multi_step_one(eng):
+    """One group of 6 fragments of 2056 payload bytes (129 or 130 source chunks: a second step of the streamer),
+    the last one shorter: waves 0 and 1 take a second fragment, loaded under a two-step one."""
+    rng = np.random.default_rng(83)
+    fr = _cut(_udp(rng, 5 * 2056 + 1001), [2056] * 5 + [1001], 0x804)
+    st, dg = _run(eng, fr, [(0, 6)], seed=84, accept=True)
+    assert int(dg[0]["copied"]) == 1 and int(dg[0]["len"]) == 5 * 2056 + 1001
+
+
 # ---- 9. caps and the launch id -------------------------------------------------------------------
 
 def test_every_caps_row_and_one_record_groups(eng):

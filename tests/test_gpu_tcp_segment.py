@@ -11,6 +11,7 @@ and checks that the launch recorded is tcpcut_kernel.
 import numpy as np
 import pytest
 
+from tests import cut_ref as R
 from tests import pktgen as P
 from tests import tcp_segment_ref as T
 
@@ -44,18 +45,7 @@ def _run(eng, sends, stride=0, caps=NOCAPS, fixed=None, start=3, cap_adj=0, src_
     msss = np.array([s[3] for s in sends], np.uint16)
     lens_p = np.array([s[4] for s in sends], np.int64)
     rng = np.random.default_rng(seed)
-    if fixed is not None:
-        rstride, base = fixed
-        buf = rng.integers(0, 256, base + n * rstride + 64, dtype=np.uint8)
-        offs = base + np.arange(n, dtype=np.uint64) * rstride
-        for o, r in zip(offs, recs):
-            assert len(r) <= rstride
-            buf[int(o):int(o) + len(r)] = np.frombuffer(r, np.uint8)
-        lens = np.full(n, rstride, np.uint32)
-        assert (kinds == kinds[0]).all() and (flags_a == flags_a[0]).all()
-    else:
-        buf, offs, lens = P.pack(recs, gap_rng=rng)
-    placed = [bytes(buf[int(o):int(o) + int(ln)]) for o, ln in zip(offs, lens)]
+    buf, offs, lens, placed = R.place_records(recs, kinds, flags_a, fixed, rng)
     so, pos = [], 0
     for i in range(n):
         if src_mod is not None:
@@ -63,37 +53,20 @@ def _run(eng, sends, stride=0, caps=NOCAPS, fixed=None, start=3, cap_adj=0, src_
         so.append(pos)
         pos += int(lens_p[i])
     src = rng.integers(0, 256, max(pos, 1), dtype=np.uint8)
-    # a first pass of the helper with caps of 0 reports what every send needs
-    size = T.expected(placed, kinds, flags_a, E.make_tcpplans(so, lens_p, msss, np.zeros(n), 0), src, stride, caps, 1)[0]
-    need = np.where(size["count"] > 0, (size["count"].astype(np.int64) - 1) *
-                    np.where(stride, stride, size["frame_len"]).astype(np.int64) + size["last_len"], 0)
-    slot = np.concatenate([[start], start + np.cumsum(need)]).astype(np.int64)
-    arena_size = int(slot[-1]) + 21
-    plans = E.make_tcpplans(so, lens_p, msss, slot[:-1], np.maximum(need + cap_adj, 0))
-    plans["reserved"], plans["reserved2"] = 0xDEAD, 0xDEADBEEF  # the kernel ignores them
-    ref_out, ref_arena = T.expected(placed, kinds, flags_a, plans, src, stride, caps, arena_size)
 
-    if fixed is not None:
-        batch = E.Batch.fixed(n, fixed[0], fixed[0], int(kinds[0]), flags=int(flags_a[0]))
-    else:
-        batch = E.Batch.from_records(offs, lens, kinds, "cuda:0", flags=flags_a)
-    d = torch.from_numpy(buf.copy()).cuda()
-    dv = d[fixed[1]:] if fixed is not None else d
+    def make_plans(dst_offsets, dst_caps):
+        plans = E.make_tcpplans(so, lens_p, msss, dst_offsets, dst_caps)
+        plans["reserved"], plans["reserved2"] = 0xDEAD, 0xDEADBEEF  # the kernel ignores them
+        return plans
+
+    plans, slots, ref_out, ref_arena = R.plan_slots(
+        n, make_plans, lambda pl, size: T.expected(placed, kinds, flags_a, pl, src, stride, caps, size), stride, start, cap_adj)
+    batch, d, dv, dst, pd = R.upload(E, buf, offs, lens, kinds, flags_a, fixed, plans, ref_arena.size)
     ds = torch.from_numpy(src.copy()).cuda()
-    dst = torch.full((arena_size,), T.SENTINEL, dtype=torch.uint8, device="cuda")
-    pd = torch.from_numpy(plans.view(np.uint8).copy()).cuda()
     out = eng.tcp_segment_emit(dv, batch, ds, dst, pd, frame_stride=stride, caps=caps)
-    launched = eng.last_launch()
-    got_out = out.cpu().numpy().reshape(-1).view(E.TCPOUT_DTYPE)
-    got_dst = dst.cpu().numpy()
-    assert launched["kernel"] == "tcpcut_kernel", launched
-    assert np.array_equal(d.cpu().numpy(), buf), "the batch buffer is only read"
-    assert np.array_equal(ds.cpu().numpy(), src), "the payload source is only read"
-    bad = np.nonzero(got_out != ref_out)[0]
-    assert bad.size == 0, f"entries differ at {bad[:8]}: got {got_out[bad[:4]]} want {ref_out[bad[:4]]}"
-    diff = np.nonzero(got_dst != ref_arena)[0]
-    assert diff.size == 0, f"destination bytes differ at {diff[:8]} (got {got_dst[diff[:8]]} want {ref_arena[diff[:8]]})"
-    return got_out, got_dst, slot[:-1], plans
+    got_out, got_dst = R.compare(eng, "tcpcut_kernel", out, dst, ref_out, ref_arena,
+                                 [(d, buf, "the batch buffer"), (ds, src, "the payload source")])
+    return got_out, got_dst, slots, plans
 
 
 # ---- 1. the size sweep ---------------------------------------------------------------------------

@@ -14,16 +14,16 @@ one box; reported per launch: the median round, and the fastest and slowest.  Ra
 """
 from __future__ import annotations
 
-import argparse
 import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
+
+import exp_common as X  # noqa: E402  (beside this script)
 
 
 def make_batches(E, eng, cfg: str, n: int, dev, count: int):
@@ -62,32 +62,22 @@ def run(cfg: str, n: int, batches: int, launches: int, rounds: int, device: int 
     launched = {}
 
     def fields_op(form):
-        def op(buf):
+        def op(i):
             eng.set_fields_kernel(form)
-            eng.emit_fields(buf, batch, fields=fields)
+            eng.emit_fields(bufs[i], batch, fields=fields)
             eng.set_fields_kernel(0)
         return op
 
-    ops = {"emit_in_place": lambda buf: eng.emit(buf, batch),
-           "verify": lambda buf: eng.verify(buf, batch, status=status),
-           "fields_auto": fields_op(0), "fields_walk": fields_op(1)}
-    ops["fields_dwalk" if cfg == "c3" else "fields_xwalk"] = fields_op(3 if cfg == "c3" else 2)
-    for name, op in ops.items():  # warm-up: every kernel loaded, every batch touched
-        for b in bufs:
-            op(b)
+    def note(name):
         ll = eng.last_launch()
         launched[name] = f'{ll["kernel"]}/{ll["variant"]} {ll["G"]}x{ll["U"]}'
-    torch.cuda.synchronize()
-    times = {name: [] for name in ops}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(rounds):
-        for name, op in ops.items():
-            e0.record()
-            for i in range(launches):
-                op(bufs[i % len(bufs)])
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1) / launches)
+
+    ops = {"emit_in_place": lambda i: eng.emit(bufs[i], batch),
+           "verify": lambda i: eng.verify(bufs[i], batch, status=status),
+           "fields_auto": fields_op(0), "fields_walk": fields_op(1)}
+    ops["fields_dwalk" if cfg == "c3" else "fields_xwalk"] = fields_op(3 if cfg == "c3" else 2)
+    X.warm_up(ops, len(bufs), after=note)
+    times = X.time_interleaved(ops, len(bufs), launches, rounds)
     # the entries are the in-place emit's fields: checked once here, on the last batch
     eng.set_fields_kernel(0)
     eng.emit_fields(bufs[-1], batch, fields=fields)
@@ -95,10 +85,7 @@ def run(cfg: str, n: int, batches: int, launches: int, rounds: int, device: int 
     res = {"config": cfg, "records": n, "read_bytes": read, "entry_bytes": 16 * n, "batches": len(bufs),
            "launches_per_round": launches, "rounds": rounds, "kernels": launched,
            "entries_with_a_field": int((f["off"] != 0xFFFF).any(axis=1).sum())}
-    for name, t in times.items():
-        med = statistics.median(t)
-        res[name] = {"ms": round(med, 4), "min_ms": round(min(t), 4), "max_ms": round(max(t), 4),
-                     "read_GBs": round(read / med / 1e6, 1)}
+    X.summarize(res, times, read, "read_GBs")
     res["fields_auto_over_emit"] = round(res["fields_auto"]["ms"] / res["emit_in_place"]["ms"], 3)
     res["fields_auto_over_verify"] = round(res["fields_auto"]["ms"] / res["verify"]["ms"], 3)
     eng.close()
@@ -114,7 +101,6 @@ def sweep(lengths, batches: int, launches: int, rounds: int, device: int = 0):
     dev = torch.device("cuda", device)
     eng = E.ChecksumEngine(device)
     out = []
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for L in lengths:
         for stride in (L, L + 64):
             n = max(1024, (3 << 29) // stride)
@@ -128,28 +114,17 @@ def sweep(lengths, batches: int, launches: int, rounds: int, device: int = 0):
             status = torch.empty(n, dtype=torch.uint8, device=dev)
 
             def fields_op(form):
-                def op(buf):
+                def op(i):
                     eng.set_fields_kernel(form)
-                    eng.emit_fields(buf, batch, fields=fields)
+                    eng.emit_fields(bufs[i], batch, fields=fields)
                     eng.set_fields_kernel(0)
                 return op
 
-            ops = {"walk": fields_op(1), "xwalk": fields_op(2), "verify": lambda buf: eng.verify(buf, batch, status=status)}
-            for op in ops.values():
-                for b in bufs:
-                    op(b)
-            torch.cuda.synchronize()
-            t = {k: [] for k in ops}
-            for _ in range(rounds):
-                for k, op in ops.items():
-                    e0.record()
-                    for i in range(launches):
-                        op(bufs[i % len(bufs)])
-                    e1.record()
-                    e1.synchronize()
-                    t[k].append(e0.elapsed_time(e1) / launches)
+            ops = {"walk": fields_op(1), "xwalk": fields_op(2), "verify": lambda i: eng.verify(bufs[i], batch, status=status)}
+            X.warm_up(ops, len(bufs))
+            med = X.summarize({}, X.time_interleaved(ops, len(bufs), launches, rounds), n * L)
             row = {"len": L, "stride": stride, "records": n}
-            row.update({k + "_ms": round(statistics.median(v), 4) for k, v in t.items()})
+            row.update({k + "_ms": v["ms"] for k, v in med.items()})
             row["xwalk_over_walk"] = round(row["xwalk_ms"] / row["walk_ms"], 3)
             out.append(row)
             print(json.dumps(row), flush=True)
@@ -159,13 +134,8 @@ def sweep(lengths, batches: int, launches: int, rounds: int, device: int = 0):
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--configs", default="c2,c4,c3")
+    ap = X.parser("c2,c4,c3", batches=4, launches=16)
     ap.add_argument("--records", type=int, default=1 << 20)
-    ap.add_argument("--batches", type=int, default=4)
-    ap.add_argument("--launches", type=int, default=16)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--out", default=None)
     ap.add_argument("--sweep", default=None, help="comma-separated record lengths (1024 .. 16257)")
     args = ap.parse_args()
     if args.sweep:
@@ -174,12 +144,7 @@ def main():
             with open(args.out, "w") as fh:
                 fh.write("".join(json.dumps(r) + "\n" for r in rows))
         return
-    out = [run(c, args.records, args.batches, args.launches, args.rounds) for c in args.configs.split(",")]
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    X.run_configs(args, lambda c: run(c, args.records, args.batches, args.launches, args.rounds))
 
 
 if __name__ == "__main__":

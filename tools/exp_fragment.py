@@ -21,16 +21,15 @@ are compared with (b)'s on the first batch.
 """
 from __future__ import annotations
 
-import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
+
+import exp_common as X  # noqa: E402  (beside this script)
 
 CONFIGS = {"8k": (1 << 14, 8192, 1500), "64k": (1 << 11, 65515, 1500), "1500": (1 << 16, 1480, 576)}
 
@@ -103,10 +102,7 @@ def run(cfg: str, batches: int, launches: int, rounds: int, device: int = 0) -> 
         "emit_then_copies": copies,
         "fragment_emit": lambda i: eng.fragment_emit(bufs[i], batch, fused, plans, frame_stride=mtu, out=out),
     }
-    for op in ops.values():  # warm-up: every kernel loaded, every batch touched
-        for i in range(len(bufs)):
-            op(i)
-    torch.cuda.synchronize()
+    X.warm_up(ops, len(bufs))
 
     # results must not change: the fused call's frames against emit + copies, on the first batch
     fused.zero_()
@@ -119,44 +115,20 @@ def run(cfg: str, batches: int, launches: int, rounds: int, device: int = 0) -> 
              "written": int(oe["written"].sum()), "frames": int(oe["count"].astype(np.uint64).sum()),
              "status_zero": bool((oe["status"] == 0).all())}
 
-    times = {name: [] for name in ops}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(rounds):
-        for name, op in ops.items():
-            e0.record()
-            for i in range(launches):
-                op(i % len(bufs))
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1) / launches)
+    times = X.time_interleaved(ops, len(bufs), launches, rounds)
     payload = nd * T
     res = {"config": cfg, "datagrams": nd, "datagram_bytes": T, "ip_mtu": mtu, "frames_per_datagram": nfrag,
            "payload_bytes": payload, "batches": len(bufs), "launches_per_round": launches, "rounds": rounds,
            "kernel": f'{launched["kernel"]} {launched["G"]}x{launched["U"]}', "check": check}
-    for name, tt in times.items():
-        med = statistics.median(tt)
-        res[name] = {"ms": round(med, 4), "min_ms": round(min(tt), 4), "max_ms": round(max(tt), 4),
-                     "payload_GBs": round(payload / med / 1e6, 1)}
-    for base in ("emit", "emit_then_copies"):
-        res["fragment_emit"]["over_" + base] = round(res["fragment_emit"]["ms"] / res[base]["ms"], 3)
+    X.summarize(res, times, payload)
+    X.over(res, "fragment_emit", ("emit", "emit_then_copies"))
     eng.close()
     return res
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--configs", default="8k,64k,1500")
-    ap.add_argument("--batches", type=int, default=3)
-    ap.add_argument("--launches", type=int, default=8)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    out = [run(c, args.batches, args.launches, args.rounds) for c in args.configs.split(",")]
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    args = X.parser("8k,64k,1500", batches=3, launches=8).parse_args()
+    X.run_configs(args, lambda c: run(c, args.batches, args.launches, args.rounds))
 
 
 if __name__ == "__main__":

@@ -22,16 +22,15 @@ frames are compared with (a)'s on the first batch.
 """
 from __future__ import annotations
 
-import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
+
+import exp_common as X  # noqa: E402  (beside this script)
 
 CONFIGS = {"64k": (1 << 14, 65536, 1460), "8k": (1 << 16, 8192, 1460), "1460": (1 << 18, 1460, 536)}
 HL, TSTRIDE = 54, 64
@@ -104,10 +103,7 @@ def run(cfg: str, batches: int, launches: int, rounds: int, device: int = 0) -> 
         "device_copy": lambda i: flat.copy_(srcs[i]),
         "tcp_segment_emit": lambda i: eng.tcp_segment_emit(tbuf, tbatch, srcs[i], fused, plans, frame_stride=S, out=out),
     }
-    for op in ops.values():  # warm-up: every kernel loaded, every batch touched
-        for i in range(len(srcs)):
-            op(i)
-    torch.cuda.synchronize()
+    X.warm_up(ops, len(srcs))
 
     # results must not change: the fused call's frames against copy_emit's, on the first batch
     eng.copy_emit(ring, fbatch, srcs[0], copies)
@@ -120,48 +116,21 @@ def run(cfg: str, batches: int, launches: int, rounds: int, device: int = 0) -> 
              "frames": int(oe["count"].astype(np.uint64).sum()), "status_zero": bool((oe["status"] == 0).all()),
              "verify_accepts_all": bool((st & E.ST_ACCEPT).all())}
 
-    times = {name: [] for name in ops}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(rounds):
-        for name, op in ops.items():
-            e0.record()
-            for i in range(launches):
-                op(i % len(srcs))
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1) / launches)
+    times = X.time_interleaved(ops, len(srcs), launches, rounds)
     payload = nd * L
     res = {"config": cfg, "sends": nd, "send_bytes": L, "mss": mss, "frames_per_send": count, "header_bytes": HL,
            "frame_stride": S, "payload_bytes": payload, "batches": len(srcs), "launches_per_round": launches,
            "rounds": rounds, "kernel": f'{launched["kernel"]} {launched["G"]}x{launched["U"]}',
            "copy_emit_kernel": f'{route["kernel"]} v{route["variant"]} {route["G"]}x{route["U"]}', "check": check}
-    for name, tt in times.items():
-        med = statistics.median(tt)
-        res[name] = {"ms": round(med, 4), "min_ms": round(min(tt), 4), "max_ms": round(max(tt), 4),
-                     "payload_GBs": round(payload / med / 1e6, 1)}
-    for base in ("copy_emit", "device_copy"):
-        res["tcp_segment_emit"]["over_" + base] = round(res["tcp_segment_emit"]["ms"] / res[base]["ms"], 3)
+    X.summarize(res, times, payload)
+    X.over(res, "tcp_segment_emit", ("copy_emit", "device_copy"))
     eng.close()
     return res
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--configs", default="64k,8k,1460")
-    ap.add_argument("--batches", type=int, default=2)
-    ap.add_argument("--launches", type=int, default=8)
-    ap.add_argument("--rounds", type=int, default=7)
-    ap.add_argument("--out", default=None)
-    args = ap.parse_args()
-    out = []
-    for c in args.configs.split(","):
-        out.append(run(c, args.batches, args.launches, args.rounds))
-        print(json.dumps(out[-1]), flush=True)
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    args = X.parser("64k,8k,1460", batches=2, launches=8).parse_args()
+    X.run_configs(args, lambda c: run(c, args.batches, args.launches, args.rounds))
 
 
 if __name__ == "__main__":

@@ -25,16 +25,15 @@ status and delivered bytes are compared with the two-pass route's on the first b
 """
 from __future__ import annotations
 
-import argparse
-import json
 import os
-import statistics
 import sys
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 import numpy as np  # noqa: E402
+
+import exp_common as X  # noqa: E402  (beside this script)
 
 SHAPE_NAMES = {-1: "auto", 0: "8x6", 1: "16x3", 4: "32x4", 6: "64x4", 7: "8x7", 8: "16x4"}
 
@@ -103,12 +102,12 @@ def run(cfg: str, n: int, batches: int, launches: int, rounds: int, shapes, devi
             ops[f"verify_copy_{'nt' if nt else 'plain'}_{SHAPE_NAMES.get(shape, shape)}"] = vcopy_op(nt, shape)
 
     launched = {}
-    for name, op in ops.items():  # warm-up: every kernel loaded, every batch touched
-        for i in range(len(bufs)):
-            op(i)
+
+    def note(name):
         ll = eng.last_launch()
         launched[name] = f'{ll["kernel"]}/{ll["variant"]} {ll["G"]}x{ll["U"]}'
-    torch.cuda.synchronize()
+
+    X.warm_up(ops, len(bufs), after=note)
 
     # results must not change: the fused call against the two passes, on the first batch
     ref_st = eng.verify(bufs[0], batch).clone()
@@ -130,22 +129,10 @@ def run(cfg: str, n: int, batches: int, launches: int, rounds: int, shapes, devi
         check["sampled_payloads_equal_records"] = ok
         del hb, hd
 
-    times = {name: [] for name in ops}
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    for _ in range(rounds):
-        for name, op in ops.items():
-            e0.record()
-            for i in range(launches):
-                op(i % len(bufs))
-            e1.record()
-            e1.synchronize()
-            times[name].append(e0.elapsed_time(e1) / launches)
+    times = X.time_interleaved(ops, len(bufs), launches, rounds)
     res = {"config": cfg, "records": n, "read_bytes": read, "delivered_bytes": check["delivered_bytes"],
            "batches": len(bufs), "launches_per_round": launches, "rounds": rounds, "kernels": launched, "check": check}
-    for name, t in times.items():
-        med = statistics.median(t)
-        res[name] = {"ms": round(med, 4), "min_ms": round(min(t), 4), "max_ms": round(max(t), 4),
-                     "read_GBs": round(read / med / 1e6, 1)}
+    X.summarize(res, times, read, "read_GBs")
     if fixed:
         for name in ops:
             if name.startswith("verify_copy_"):
@@ -155,22 +142,12 @@ def run(cfg: str, n: int, batches: int, launches: int, rounds: int, shapes, devi
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--configs", default="c2,c4,c3")
+    ap = X.parser("c2,c4,c3", batches=4, launches=16)
     ap.add_argument("--records", type=int, default=1 << 20)
-    ap.add_argument("--batches", type=int, default=4)
-    ap.add_argument("--launches", type=int, default=16)
-    ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--shapes", default="8", help="comma-separated launch shapes (CFG_*) besides the library's choice")
-    ap.add_argument("--out", default=None)
     args = ap.parse_args()
     shapes = [int(x) for x in args.shapes.split(",") if x]
-    out = [run(c, args.records, args.batches, args.launches, args.rounds, shapes) for c in args.configs.split(",")]
-    text = json.dumps(out, indent=1)
-    print(text)
-    if args.out:
-        with open(args.out, "w") as fh:
-            fh.write(text + "\n")
+    X.run_configs(args, lambda c: run(c, args.records, args.batches, args.launches, args.rounds, shapes))
 
 
 if __name__ == "__main__":
