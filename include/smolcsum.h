@@ -33,6 +33,9 @@
  *         datagram cut into the frames the iface sends (dispatch_ip's and dispatch_ipv4_frag's copy);
  *       - smol_csum_batch_tcp_segment_emit == emit over TCP header templates, and in the same pass each
  *         send's payload cut into MSS-sized segments behind them (TcpSocket::dispatch's burst);
+ *       - smol_csum_batch_verify_tcp_assemble == verify over the frames of TCP connections, and in the
+ *         same pass each segment's payload put at its sequence number's place in the connection's
+ *         receive ring, trimmed to the window (TcpSocket::process' write_unallocated);
  *       - smol_csum_batch_data   == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
@@ -672,6 +675,141 @@ int smol_csum_batch_tcp_segment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf,
                                      const smol_checksum_caps_t* caps, const uint8_t* d_src, uint8_t* d_dst,
                                      const smol_csum_tcpplan_t* d_plans, uint32_t frame_stride,
                                      smol_csum_tcpout_t* d_out, void* stream);
+
+#define SMOL_MAX_FLOW_SEGMENTS 256u
+
+/* One connection's receive window (32 bytes, 16-byte-aligned device array, input; one per GROUP). */
+typedef struct {
+    uint64_t dst_offset;   /* byte offset of the ring's storage in d_dst (any alignment)                 */
+    uint32_t ring_len;     /* bytes of ring storage (rx_buffer.capacity())                                */
+    uint32_t ring_pos;     /* ring index of the window's first byte (rx_buffer.get_idx(rx_buffer.len()))  */
+    uint32_t window_start; /* sequence number of that byte: remote_seq_no + rx_buffer.len()               */
+    uint32_t window_len;   /* window_end - window_start (0: remote_last_ack is None, or a closed window)  */
+    uint32_t reserved[2];  /* must be 0 */
+} smol_csum_tcpwin_t;
+
+/* One record's outcome (16 bytes, 16-byte-aligned device array, output; one per RECORD). */
+typedef struct {
+    uint32_t seq;      /* the TCP sequence number field (0 without SMOL_SEG_TCP)                        */
+    uint32_t win_off;  /* overlap_start - window_start: window offset of the first delivered byte       */
+    uint32_t len;      /* overlap_end - overlap_start: bytes of the payload inside the window           */
+    uint16_t off;      /* record-relative offset of the payload, untrimmed (smol_csum_span_t.off)       */
+    uint8_t flags;     /* SMOL_SEG_*                                                                     */
+    uint8_t reserved;  /* 0 */
+} smol_csum_tcpseg_t;
+#define SMOL_SEG_TCP         0x01u /* the record has a TCP payload span under verify_copy's span rule    */
+#define SMOL_SEG_IN_WINDOW   0x02u /* segment_in_window (tcp.rs:1719-1769) against the group's window    */
+#define SMOL_SEG_COPIED      0x04u /* IN_WINDOW, neither SYN nor RST: its len bytes were stored (len may be 0) */
+#define SMOL_SEG_REDELIVERED 0x08u /* stored a second time after the group's verdicts (see Overlaps)     */
+
+/* One connection's outcome (16 bytes, 16-byte-aligned device array, output; one per GROUP). */
+typedef struct {
+    uint32_t contig_len;  /* bytes now contiguous from window_start: what enqueue_unallocated gets in total */
+    uint32_t counted;     /* records that count into it (below)                                            */
+    uint32_t redelivered; /* records with SMOL_SEG_REDELIVERED                                             */
+    uint8_t valid;        /* 1: the group and its window were usable                                       */
+    uint8_t reserved[3];  /* 0 */
+} smol_csum_tcpflow_t;
+
+/* verify, and every TCP segment's payload delivered to the place its sequence number gives it in its
+ * connection's receive ring, trimmed to the receive window, in one pass over the frames: the receive
+ * counterpart of smol_csum_batch_tcp_segment_emit, whose output is this call's input (as fragment_emit's is
+ * verify_reassemble's).  In TcpSocket::process (src/socket/tcp.rs:1705-1783, 2205-2241) the place of a
+ * payload follows from the segment's own sequence number: the segment is tested against the receive
+ * window (segment_in_window), trimmed to it at both ends, written with
+ * rx_buffer.write_unallocated(payload_offset, payload), which wraps around the ring
+ * (src/storage/ring_buffer.rs:321-338), and the assembler then says how much of the front has become
+ * contiguous (add_then_remove_front).  TcpRepr::parse has summed the payload before
+ * (src/wire/tcp.rs:917-919): two passes over it.  Here each frame byte is read once.
+ *
+ * Groups.  smol_csum_frag_group_t is reused unchanged: a group is the frames of one connection that
+ * arrived in one poll, `count` consecutive records from `first`, in arrival order.  The caller
+ * demultiplexes, as it forms fragment groups.  d_wins and d_flows have one entry per GROUP, d_status and
+ * d_segs one per RECORD.  A group is invalid when first >= n, count > n - first, count is 0 or above
+ * SMOL_MAX_FLOW_SEGMENTS, the group's or the window's reserved words are not 0, window_len > ring_len,
+ * or ring_pos >= ring_len while ring_len > 0 (with ring_len == 0, ring_pos must be 0).  For an invalid
+ * group no record is read, no status byte or segment entry is written, nothing is stored, and the flow
+ * entry is all zero.  Records outside every group are not written.  Groups must not share records.
+ *
+ * Status.  d_status[i] is exactly the byte smol_csum_batch_verify writes for record i under caps: per
+ * record, not combined over the group, because TCP segments are independent packets.
+ *
+ * Span.  A record has SMOL_SEG_TCP when smol_csum_batch_verify_copy would give it a span and the protocol
+ * is TCP; off is then verify_copy's off, and the payload length is p = L4 buffer length - 4 * data offset
+ * (Ethernet padding is excluded).  Every other record (UDP, ICMP, IGMP, malformed, unsupported, fragments,
+ * SMOL_REC_IPHDR_ONLY, SMOL_KIND_RAW, non-IP ethertypes) gets an all-zero entry and stores nothing.
+ *
+ * Window rule (tcp.rs:1719-1783).  Sequence arithmetic is TcpSeqNumber's: s = (int32)(seq - window_start),
+ * W = window_len.
+ *   p == 0: not in the window when s == -1 (a keep-alive or a window probe); with W == 0 in the window iff
+ *           s == 0; otherwise iff 0 <= s < W.
+ *   p > 0:  not in the window when W == 0; otherwise in the window iff (0 <= s < W) or (0 < s + p <= W).
+ *           A segment that starts before the window and ends past it is NOT in the window: this is the
+ *           reference's rule.
+ * In the window: win_off = max(0, s), len = min(W, s + p) - max(0, s), and the delivered bytes are payload
+ * bytes [max(0, -s), max(0, -s) + len).  Not in the window: win_off = len = 0.  A record with SYN or RST
+ * set reports SMOL_SEG_IN_WINDOW, win_off and len by the same formula and is never SMOL_SEG_COPIED: the
+ * stack treats such segments on their own paths.
+ *
+ * Placement.  Window offset w lives at d_dst[dst_offset + (ring_pos + w) % ring_len].  Because
+ * len <= window_len <= ring_len, a delivered range is at most two contiguous pieces: write_unallocated's
+ * two get_unallocated slices.
+ *
+ * THE COPY DOES NOT WAIT FOR THE VERDICT, as in smol_csum_batch_verify_copy.
+ *
+ * Overlaps.  Unlike verify_copy's slots, the ranges of a group's records may coincide (retransmissions,
+ * out-of-order arrivals).  A DELIVERED record is one with SMOL_SEG_COPIED and len > 0; a COUNTED record is
+ * a delivered one whose status has SMOL_ST_ACCEPT.  Once every verdict of the group is known and every
+ * first-pass store of the group is complete, each counted record whose window range intersects the range
+ * of a delivered record that is not counted is stored again, whole, and gets SMOL_SEG_REDELIVERED: the
+ * case of a corrupted segment and its retransmission in one poll.  After the call:
+ *   - every window byte covered by at least one counted record holds the byte of a counted record that
+ *     covers it;
+ *   - where several counted records cover a byte with different values, which of them it holds is
+ *     unspecified (an honest sender's retransmissions agree, and the reference itself is order-dependent
+ *     there);
+ *   - bytes covered only by records that are not counted hold those records' bytes: they lie in
+ *     unallocated ring space, which the caller never commits.
+ *
+ * Flow entry.  contig_len is the largest c such that the union of the counted records' window ranges
+ * covers [0, c); counted and redelivered count those records; valid is 1.
+ *
+ * What stays with the caller.
+ *   - ACK acceptability and the socket state machine.  contig_len is valid for a caller that processes
+ *     every counted record; a caller that drops a counted record for socket-state reasons rebuilds the
+ *     coverage from the segment entries with its own Assembler.
+ *   - The assembler's hole limit.  The reference's ASSEMBLER_MAX_SEGMENT_COUNT is 4 holes; this call
+ *     computes the unbounded union.
+ *   - The window does not move inside one call.  Every record is tested against the window as it stood at
+ *     the start of the poll, while the reference advances window_start segment by segment.  For segments
+ *     whose overlapping bytes agree and which all end at or before window_end, the ring bytes
+ *     [0, contig_len) and contig_len itself equal what feeding the counted records to the socket one by
+ *     one gives (with an unbounded assembler).  Two differences: a duplicate of data enqueued earlier in
+ *     the same poll is reported SMOL_SEG_IN_WINDOW here; a segment that starts before the advanced
+ *     window_start and ends past window_end is dropped by the reference and trimmed and delivered here.
+ *   - No flow-key check.  A record of another connection inside a group is placed like any other.
+ *
+ * Writes.  No byte of d_dst is ever read and none outside the delivered ranges is ever written.  Edges go
+ * out as byte-masked stores, never read-modify-write.  Rings of different groups must not overlap each
+ * other or the batch.  d_buf is only read, and only in 16-byte chunks that hold at least one byte of a
+ * record.
+ *
+ * Resources.  No context scratch, no event, no allocation; stream-ordered on `stream`, graph-capturable,
+ * and calls on different streams are independent (also on one context).
+ *
+ * SMOL_EINVAL: NULL ctx, bad caps, NULL d_groups / d_dst / d_wins / d_status / d_segs / d_flows with
+ * n_groups > 0, d_groups, d_wins, d_segs or d_flows not 16-byte aligned.  SMOL_ERANGE: as verify.
+ * n_groups == 0 returns SMOL_OK and launches nothing.
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive, as tcp_segment_emit was). */
+int smol_csum_batch_verify_tcp_assemble(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
+                                        const smol_csum_frag_group_t* d_groups, uint64_t n_groups,
+                                        const smol_checksum_caps_t* caps, uint8_t* d_dst,
+                                        const smol_csum_tcpwin_t* d_wins,   /* one per GROUP  */
+                                        uint8_t* d_status,                  /* one per RECORD */
+                                        smol_csum_tcpseg_t* d_segs,         /* one per RECORD */
+                                        smol_csum_tcpflow_t* d_flows,       /* one per GROUP  */
+                                        void* stream);
 
 /* ---- 4. 6LoWPAN next-header-compressed UDP (RFC 6282 §4.3) ------------------------------- */
 

@@ -34,7 +34,7 @@ ABI_SYMBOLS = [
     "smol_csum_batch_verify_copy",
     "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
     "smol_csum_batch_verify_frag", "smol_csum_batch_verify_reassemble", "smol_csum_batch_fragment_emit",
-    "smol_csum_batch_tcp_segment_emit", "smol_csum_batch_nhc_udp_emit",
+    "smol_csum_batch_tcp_segment_emit", "smol_csum_batch_verify_tcp_assemble", "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
 ]
 TOOL_SYMBOLS = [
@@ -192,6 +192,44 @@ class TcpOutC(ctypes.Structure):
     ]
 
 
+class TcpWinC(ctypes.Structure):
+    """smol_csum_tcpwin_t: one connection's receive window and ring (smol_csum_batch_verify_tcp_assemble)."""
+
+    _fields_ = [
+        ("dst_offset", ctypes.c_uint64),
+        ("ring_len", ctypes.c_uint32),
+        ("ring_pos", ctypes.c_uint32),
+        ("window_start", ctypes.c_uint32),
+        ("window_len", ctypes.c_uint32),
+        ("reserved", ctypes.c_uint32 * 2),
+    ]
+
+
+class TcpSegC(ctypes.Structure):
+    """smol_csum_tcpseg_t: one record's outcome (smol_csum_batch_verify_tcp_assemble)."""
+
+    _fields_ = [
+        ("seq", ctypes.c_uint32),
+        ("win_off", ctypes.c_uint32),
+        ("len", ctypes.c_uint32),
+        ("off", ctypes.c_uint16),
+        ("flags", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8),
+    ]
+
+
+class TcpFlowC(ctypes.Structure):
+    """smol_csum_tcpflow_t: one connection's outcome (smol_csum_batch_verify_tcp_assemble)."""
+
+    _fields_ = [
+        ("contig_len", ctypes.c_uint32),
+        ("counted", ctypes.c_uint32),
+        ("redelivered", ctypes.c_uint32),
+        ("valid", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 3),
+    ]
+
+
 _LIBS = {}
 
 
@@ -258,6 +296,10 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.smol_csum_batch_tcp_segment_emit.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps), vp, vp, vp, u32,
                                                        vp, vp]
         L.smol_csum_batch_tcp_segment_emit.restype = i32
+    if hasattr(L, "smol_csum_batch_verify_tcp_assemble"):
+        L.smol_csum_batch_verify_tcp_assemble.argtypes = [vp, vp, ctypes.POINTER(BatchC), vp, u64, ctypes.POINTER(Caps),
+                                                          vp, vp, vp, vp, vp, vp]
+        L.smol_csum_batch_verify_tcp_assemble.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []

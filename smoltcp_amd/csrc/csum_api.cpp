@@ -449,6 +449,26 @@ int smol_csum_batch_tcp_segment_emit(smol_csum_ctx_t* ctx, const uint8_t* d_buf,
     return on_device(ctx, "tcp_segment_emit kernel launch", [&] { return launch_tcpcut(p, v, (hipStream_t)stream); });
 }
 
+// Verify with every TCP segment's payload delivered to its sequence number's place in its connection's
+// receive ring in the same pass (include/smolcsum.h).  Uses none of the context's scratch or events, so calls
+// on different streams are independent.
+int smol_csum_batch_verify_tcp_assemble(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
+                                        const smol_csum_frag_group_t* d_groups, uint64_t n_groups,
+                                        const smol_checksum_caps_t* caps, uint8_t* d_dst, const smol_csum_tcpwin_t* d_wins,
+                                        uint8_t* d_status, smol_csum_tcpseg_t* d_segs, smol_csum_tcpflow_t* d_flows,
+                                        void* stream) {
+    int rc;
+    if (!begin_group_call(ctx, caps, b, d_buf, d_groups, n_groups, &rc)) return rc;
+    if (!d_dst || !d_wins || !d_status || !d_segs || !d_flows || ((uintptr_t)d_wins & 15u) != 0 ||
+        ((uintptr_t)d_segs & 15u) != 0 || ((uintptr_t)d_flows & 15u) != 0)
+        return SMOL_EINVAL;
+    KParams p = base_params(ctx, d_buf, b, caps);
+    p.status = d_status;
+    const TcpAsmArgs v = {d_dst, d_wins, d_segs, d_flows};
+    return on_device(ctx, "verify_tcp_assemble kernel launch",
+                     [&] { return launch_tcpasm(p, d_groups, n_groups, v, ctx->max_blocks, (hipStream_t)stream); });
+}
+
 // ---- 6LoWPAN NHC UDP --------------------------------------------------------------------------
 
 int smol_csum_batch_nhc_udp_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,

@@ -256,10 +256,11 @@ __device__ inline uint64_t logical_block(uint32_t xcd_remap) {
 // KERN_FRAGCOPY: smol_csum_batch_verify_reassemble's kernel (no registry row; variant 0, G 64, U its chunks per lane).
 // KERN_FRAGCUT: smol_csum_batch_fragment_emit's kernel (the same).
 // KERN_TCPCUT: smol_csum_batch_tcp_segment_emit's kernel (the same).
+// KERN_TCPASM: smol_csum_batch_verify_tcp_assemble's kernel (the same).
 enum {
     KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6,
     KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9, KERN_VCOPY = 10,
-    KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12, KERN_TCPCUT = 13
+    KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12, KERN_TCPCUT = 13, KERN_TCPASM = 14
 };
 inline std::atomic<uint32_t> g_last_launch{0};
 inline void note_launch(uint32_t kern, uint32_t var, uint32_t g, uint32_t u) {
@@ -379,6 +380,18 @@ struct TcpCutArgs {
     smol_csum_tcpout_t* out;           // one 16-B entry per record (output)
 };
 hipError_t launch_tcpcut(const KParams& p, const TcpCutArgs& v, hipStream_t s);
+// verify_tcp_assemble (smol_csum_batch_verify_tcp_assemble, csum_tcpasm.hip): verify's status bytes, and every
+// TCP segment's payload delivered to its sequence number's place in its group's receive ring in `dst`, trimmed
+// to the group's window, in the same pass.  One 256-thread workgroup per group; outside the variant registry.
+struct TcpAsmArgs {
+    uint8_t* dst;
+    const smol_csum_tcpwin_t* wins;  // one 32-B entry per group (input)
+    smol_csum_tcpseg_t* segs;        // one 16-B entry per record (output)
+    smol_csum_tcpflow_t* flows;      // one 16-B entry per group (output)
+};
+// max_blocks: the grid cap (smol_csum_tool_set_max_blocks: a few workgroups walk many groups).
+hipError_t launch_tcpasm(const KParams& p, const smol_csum_frag_group_t* groups, uint64_t ngroups,
+                         const TcpAsmArgs& v, uint32_t max_blocks, hipStream_t s);
 hipError_t launch_stream_read(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t max_blocks,
                               hipStream_t s);
 hipError_t launch_field_probe(uint8_t* buf, uint64_t bytes, uint64_t stride, uint32_t f1, uint32_t f2,

@@ -714,12 +714,15 @@ __device__ __forceinline__ void stage_record(const KParams& p, uint64_t r, bool 
 // contiguous run (8 records per wavefront: one 128-B line per store instruction).
 // FREG (with FLD; csum_fragcut.hip): lane 0's entry goes to *freg, a register of the caller's, instead of
 // p.fields: the caller writes the values where its own layout wants them.
+// st_out (MODE_VERIFY; csum_tcpasm.hip): lane 0 also leaves the status byte there (the caller's LDS), for a
+// caller that goes on working with the verdict.
 template <int G, int MODE, bool NHC, class RD, int WINB = 0, bool SEGP = false, bool NOSTORE = false,
           bool NTST = false, bool STG = false, bool FLD = false, bool FREG = false>
 __device__ __forceinline__ void finish_gates(const KParams& p, const Geom& g, uint32_t acc, const RD& rd,
                                              const uint8_t* winb, uint32_t head, uint64_t a0, uint64_t r,
                                              int lane, uint8_t* winw = nullptr, uint64_t wsA = ~0ull,
-                                             uint64_t wsB = ~0ull, int stg = 0, u32x4* freg = nullptr) {
+                                             uint64_t wsB = ~0ull, int stg = 0, u32x4* freg = nullptr,
+                                             uint32_t* st_out = nullptr) {
     static_assert(!FREG || FLD, "FREG: the fields sink in a register");
     constexpr bool EMITS = MODE == MODE_EMIT || MODE == MODE_COPY;
     const bool odd = (a0 & 1u) != 0;
@@ -916,6 +919,7 @@ __device__ __forceinline__ void finish_gates(const KParams& p, const Geom& g, ui
             if constexpr (NOSTORE) asm volatile("" ::"v"(st));  // (timing only: no status byte)
             else if constexpr (NTST) __builtin_nontemporal_store((uint8_t)st, (gu8)p.status + r);  // (verify: experiments)
             else ((gu8)p.status)[r] = (uint8_t)st;
+            if (st_out) *st_out = st;
         }
     }
 }

@@ -16,8 +16,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import (NO_FIELD, BatchC, Caps, DgramC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, TcpOutC, TcpPlanC, check,
-                   lib)
+from ._lib import (NO_FIELD, BatchC, Caps, DgramC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, TcpFlowC, TcpOutC, TcpPlanC,
+                   TcpSegC, TcpWinC, check, lib)
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -77,6 +77,18 @@ assert TCPPLAN_DTYPE.itemsize == 32 == ctypes.sizeof(TcpPlanC)
 TCPOUT_DTYPE = np.dtype([("count", "<u4"), ("frame_len", "<u4"), ("last_len", "<u4"), ("status", "u1"), ("written", "u1"),
                          ("reserved", "<u2")])
 assert TCPOUT_DTYPE.itemsize == 16 == ctypes.sizeof(TcpOutC)
+# smol_csum_tcpwin_t / smol_csum_tcpseg_t / smol_csum_tcpflow_t: a connection's receive window, a record's and a
+# connection's outcome (smol_csum_batch_verify_tcp_assemble)
+TCPWIN_DTYPE = np.dtype([("dst_offset", "<u8"), ("ring_len", "<u4"), ("ring_pos", "<u4"), ("window_start", "<u4"),
+                         ("window_len", "<u4"), ("reserved", "<u4", (2,))])
+assert TCPWIN_DTYPE.itemsize == 32 == ctypes.sizeof(TcpWinC)
+TCPSEG_DTYPE = np.dtype([("seq", "<u4"), ("win_off", "<u4"), ("len", "<u4"), ("off", "<u2"), ("flags", "u1"), ("reserved", "u1")])
+assert TCPSEG_DTYPE.itemsize == 16 == ctypes.sizeof(TcpSegC)
+TCPFLOW_DTYPE = np.dtype([("contig_len", "<u4"), ("counted", "<u4"), ("redelivered", "<u4"), ("valid", "u1"),
+                          ("reserved", "u1", (3,))])
+assert TCPFLOW_DTYPE.itemsize == 16 == ctypes.sizeof(TcpFlowC)
+MAX_FLOW_SEGMENTS = 256
+SEG_TCP, SEG_IN_WINDOW, SEG_COPIED, SEG_REDELIVERED = 0x01, 0x02, 0x04, 0x08  # SMOL_SEG_*
 
 
 def make_slots(dst_offsets, caps) -> np.ndarray:
@@ -109,6 +121,18 @@ def make_tcpplans(src_offsets, lens, msss, dst_offsets, caps) -> np.ndarray:
     p["dst_offset"] = np.asarray(dst_offsets, dtype=np.uint64)
     p["cap"] = np.broadcast_to(np.asarray(caps, dtype=np.uint32), (n,))
     return p
+
+
+def make_tcpwins(dst_offsets, ring_lens, ring_poss, window_starts, window_lens) -> np.ndarray:
+    """Host array of smol_csum_tcpwin_t (view it as uint8 and copy it to the device)."""
+    n = len(dst_offsets)
+    w = np.zeros(n, dtype=TCPWIN_DTYPE)
+    w["dst_offset"] = np.asarray(dst_offsets, dtype=np.uint64)
+    w["ring_len"] = np.broadcast_to(np.asarray(ring_lens, dtype=np.uint32), (n,))
+    w["ring_pos"] = np.broadcast_to(np.asarray(ring_poss, dtype=np.uint32), (n,))
+    w["window_start"] = np.broadcast_to(np.asarray(window_starts, dtype=np.uint32), (n,))
+    w["window_len"] = np.broadcast_to(np.asarray(window_lens, dtype=np.uint32), (n,))
+    return w
 
 
 def apply_fields(host_buf: np.ndarray, record_offsets, record_lens, fields) -> np.ndarray:
@@ -423,6 +447,43 @@ class ChecksumEngine:
               "smol_csum_batch_tcp_segment_emit")
         return out
 
+    def verify_tcp_assemble(self, buf, batch: Batch, groups, dst, wins, caps=None, status=None, segs=None, flows=None,
+                            stream=None):
+        """verify, and in the same pass every TCP segment's payload put at the place its sequence number gives
+        it in its connection's receive ring in `dst`, trimmed to the receive window
+        (smol_csum_batch_verify_tcp_assemble).  `groups`: a device uint8 tensor of smol_csum_frag_group_t (see
+        make_groups), one per connection: its frames of this poll, consecutive records in arrival order;
+        `wins`: a device uint8 tensor of one smol_csum_tcpwin_t per GROUP (see make_tcpwins); `dst`: the
+        destination uint8 device tensor, written only inside the delivered ranges.  Returns (status, segs,
+        flows): verify's status byte per record (a fresh tensor starts zeroed; records outside the groups keep
+        their value), an n x 16 uint8 device tensor of smol_csum_tcpseg_t (view its host copy as TCPSEG_DTYPE;
+        a fresh one starts zeroed) and an n_groups x 16 one of smol_csum_tcpflow_t (TCPFLOW_DTYPE).  The copy
+        does not wait for the verdict: commit `contig_len` bytes of a ring (enqueue_unallocated) and feed the
+        counted out-of-order entries to the socket's assembler."""
+        import torch
+
+        self._check_buf(buf, batch)
+        assert groups.is_cuda and groups.numel() % 16 == 0
+        ng = groups.numel() // 16
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert wins.is_cuda and wins.is_contiguous() and wins.numel() * wins.dtype.itemsize >= 32 * ng
+        if status is None:
+            status = torch.zeros(batch.n, dtype=torch.uint8, device=buf.device)
+        if segs is None:
+            segs = torch.zeros((batch.n, 16), dtype=torch.uint8, device=buf.device)
+        if flows is None:
+            flows = torch.empty((ng, 16), dtype=torch.uint8, device=buf.device)
+        assert segs.is_cuda and segs.is_contiguous() and segs.numel() * segs.dtype.itemsize >= 16 * batch.n
+        assert flows.is_cuda and flows.is_contiguous() and flows.numel() * flows.dtype.itemsize >= 16 * ng
+        b = batch.c()
+        c = _caps(caps)
+        check(self._L.smol_csum_batch_verify_tcp_assemble(self._h, buf.data_ptr(), ctypes.byref(b), groups.data_ptr(), ng,
+                                                        ctypes.byref(c), dst.data_ptr(), wins.data_ptr(),
+                                                        status.data_ptr(), segs.data_ptr(), flows.data_ptr(),
+                                                        self._stream(stream)),
+              "smol_csum_batch_verify_tcp_assemble")
+        return status, segs, flows
+
     def nhc_udp_emit(self, buf, batch: Batch, addrs, caps=None, status=None, stream=None):
         """6LoWPAN NHC UDP emit (smol_csum_batch_nhc_udp_emit): ``addrs`` is a device uint8 tensor of
         n x 32 bytes (IPv6 source, destination per record)."""
@@ -599,13 +660,13 @@ class ChecksumEngine:
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
         "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
-        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel", "variant": VAR, "G":
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel" | verify_tcp_assemble's "tcpasm_kernel", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
                  6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel",
-                 11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel"}
+                 11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel", 14: "tcpasm_kernel"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

@@ -293,6 +293,23 @@ public:
         check(smol_csum_batch_tcp_segment_emit(ctx_, d_buf, &bc, &cc, d_src, d_dst, d_plans, frame_stride, d_out, stream),
               "smol_csum_batch_tcp_segment_emit");
     }
+    // verify, and in the same pass every TCP segment's payload put at the place its sequence number gives it
+    // in its connection's receive ring, trimmed to the receive window (TcpSocket::process' segment_in_window,
+    // trim and rx_buffer.write_unallocated, src/socket/tcp.rs:1705-1783, 2205-2241): group k is one
+    // connection's frames of this poll in arrival order, d_wins[k] its ring and window; d_segs[i] = record i's
+    // sequence number, window range and SMOL_SEG_* flags, d_flows[k] = how far the in-order data now reaches
+    // (what enqueue_unallocated gets).  d_wins / d_flows: one per GROUP, d_status / d_segs: one per record.
+    // The copy waits for no verdict; d_buf is only read.
+    void verify_tcp_assemble(const uint8_t* d_buf, const Batch& b, const smol_csum_frag_group_t* d_groups,
+                             uint64_t n_groups, uint8_t* d_dst, const smol_csum_tcpwin_t* d_wins, uint8_t* d_status,
+                             smol_csum_tcpseg_t* d_segs, smol_csum_tcpflow_t* d_flows,
+                             const smoltcp::phy::ChecksumCapabilities& caps = {}, void* stream = nullptr) {
+        auto bc = b.c();
+        auto cc = caps.c();
+        check(smol_csum_batch_verify_tcp_assemble(ctx_, d_buf, &bc, d_groups, n_groups, &cc, d_dst, d_wins, d_status,
+                                                  d_segs, d_flows, stream),
+              "smol_csum_batch_verify_tcp_assemble");
+    }
 
     // 6LoWPAN NHC UDP (sixlowpan::nhc::UdpNhcRepr::emit / ::parse): every record is a LOWPAN_NHC
     // UDP packet; d_addrs[i] holds record i's IPv6 addresses (IPHC-decompressed).
