@@ -36,7 +36,10 @@
  *       - smol_csum_batch_verify_tcp_assemble == verify over the frames of TCP connections, and in the
  *         same pass each segment's payload put at its sequence number's place in the connection's
  *         receive ring, trimmed to the window (TcpSocket::process' write_unallocated);
- *       - smol_csum_batch_data   == checksum::data() over each raw span.
+ *       - smol_csum_batch_verify_echo_reply == verify, and in the same pass the reply to every ICMP echo
+ *         request written to a caller-chosen slot, head fresh, data echoed, checksums filled (the
+ *         iface's own responder, process_icmpv4 / process_icmpv6 and the dispatch of their reply);
+ *       - smol_csum_batch_data  == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
  *     RxToken, with the stack's default caps (Checksum::Both).
@@ -810,6 +813,101 @@ int smol_csum_batch_verify_tcp_assemble(smol_csum_ctx_t* ctx, const uint8_t* d_b
                                         smol_csum_tcpseg_t* d_segs,         /* one per RECORD */
                                         smol_csum_tcpflow_t* d_flows,       /* one per GROUP  */
                                         void* stream);
+
+/* ---- verify_echo_reply: echo requests verified, the replies written in the same pass ------- */
+
+/* What the call knows of the interface (host memory, nullable: NULL means all zero). */
+typedef struct {
+    uint8_t bcast_v4[4]; /* the iface's directed-broadcast address; 0.0.0.0: none */
+    uint8_t reserved[4]; /* must be 0 */
+} smol_csum_echo_cfg_t;
+
+/* One record's outcome (8 bytes, 8-byte-aligned device array, output). */
+typedef struct {
+    uint32_t frame_len; /* the reply's length; 0 unless SMOL_ECHO_ANSWERED                             */
+    uint16_t data_off;  /* record-relative offset of the echo data; 0 unless SMOL_ECHO_REQUEST         */
+    uint8_t head_len;   /* reply bytes in front of the data (14|0 + 20|40 + 8); 0 unless ANSWERED      */
+    uint8_t flags;      /* SMOL_ECHO_*                                                                 */
+} smol_csum_echo_t;
+#define SMOL_ECHO_REQUEST  0x01u /* a well-formed ICMPv4 / ICMPv6 echo request                           */
+#define SMOL_ECHO_ANSWERED 0x02u /* the wire-level address rule answers it: the reply frame is defined   */
+#define SMOL_ECHO_WRITTEN  0x04u /* ANSWERED and frame_len <= cap: the frame is in the slot              */
+#define SMOL_ECHO_SEND     0x08u /* WRITTEN and the request passed its checksum gates: transmit the slot */
+#define SMOL_ECHO_HOST     0x10u /* a request only the host can answer (it needs the iface's addresses)  */
+
+/* Verify, and write the reply to every ICMP echo request of the batch to its slot of d_dst, in one pass.
+ * The reference's responder makes two reads, one write and two sums over the echo data:
+ * InterfaceInner::process_icmpv4 (src/iface/interface/ipv4.rs:320-371) and process_icmpv6
+ * (src/iface/interface/ipv6.rs:399-416) parse the request, Icmpv4Repr::parse / Icmpv6Repr::parse summing the
+ * whole message; they build an EchoReply with the same ident, sequence number and data and hand it to
+ * icmpv4_reply / icmpv6_reply (ipv4.rs:373-418, ipv6.rs:538-563); dispatch then copies the data
+ * (Icmpv4Repr::emit, src/wire/icmpv4.rs:506-517; src/wire/icmpv6.rs:814-822) and sums it again
+ * (fill_checksum).  Here each request byte is read once: the registers that are summed feed the stores, and
+ * the request's sum and the reply's share everything but the message's first four bytes.
+ *
+ * Status.  d_status[i] is exactly the byte smol_csum_batch_verify writes for the same batch and caps, for
+ * every record, echo or not.
+ *
+ * REQUEST.  Set when the record reaches the ICMPv4 or ICMPv6 gate, verify's parse marks it neither
+ * SMOL_ST_MALFORMED nor SMOL_ST_UNSUPPORTED (so not for a fragment, a SMOL_REC_IPHDR_ONLY record, a
+ * Hop-by-Hop drop, a failed check_len, a non-IP ethertype or SMOL_KIND_RAW), the type is 8 (v4) or 128 (v6)
+ * and the code is 0 (icmpv4.rs:410, icmpv6.rs:689).  Then data_off = L4 offset + 8 and the data length is
+ * the L4 buffer length - 8, the L4 buffer being verify's: IPv4 total length - IHL * 4, or the IPv6 payload
+ * length less a leading Hop-by-Hop header.  Ethernet padding is neither summed nor echoed.  Every other
+ * record's entry is all zero and nothing is stored for it.
+ *
+ * Address rule.  Wire-level only: the engine holds no interface state beyond `cfg`.
+ *   nonuni4(a): a is 255.255.255.255, in 224.0.0.0/4, 0.0.0.0, or equal to a non-zero bcast_v4.
+ *   bcast4(a):  a is 255.255.255.255 or equal to a non-zero bcast_v4.
+ *   nonuni6(a): a[0] == 0xff, or a is ::.
+ *   A MAC is unicast when bit 0 of its first byte is clear.
+ *   IPv4 (icmpv4_reply): nonuni4(src): no reply, neither ANSWERED nor HOST.  Otherwise !nonuni4(dst):
+ *     ANSWERED.  Otherwise bcast4(dst): HOST (the reference answers from ipv4_addr(), which only the host
+ *     knows).  Otherwise (multicast, unspecified): none.
+ *   IPv6 (process_ipv6, ipv6.rs:198, and icmpv6_reply): nonuni6(src): none.  !nonuni6(dst): ANSWERED.
+ *     Otherwise HOST (get_source_address_ipv6).
+ *   SMOL_KIND_ETH: both MACs must be unicast, else an ANSWERED record becomes HOST (the neighbour cache and
+ *     the interface's own MAC are the host's).
+ * HOST and ANSWERED exclude each other; both imply REQUEST.
+ *
+ * The reply frame (ANSWERED records only), head_len bytes of head and then the data:
+ *   Ethernet (SMOL_KIND_ETH): dst = the request's src MAC, src = the request's dst MAC, the request's
+ *     ethertype.
+ *   IPv4, the bytes Ipv4Repr::emit writes (src/wire/ipv4.rs:584-612): 45 00, total length = 28 + data length,
+ *     ident 0, flags/offset 40 00, TTL 64, protocol 1, header checksum, src = the request's dst, dst = the
+ *     request's src.  The request's IPv4 options are not carried.
+ *   IPv6, per Ipv6Repr::emit (src/wire/ipv6.rs:631-638): 60 00 00 00, payload length = 8 + data length, next
+ *     header 58, hop limit 64, the addresses swapped.  A request's Hop-by-Hop header is not carried.
+ *   ICMP: type 0 (v4) or 129 (v6), code 0, checksum, the request's ident and sequence number, the data.
+ *   frame_len = head_len + data length.
+ * Checksums are filled as smol_csum_batch_emit would fill them on that frame under `caps`: the IPv4 header's
+ * under caps.ipv4 tx, else 0; the ICMP one under caps.icmpv4 / caps.icmpv6 tx, else 0; no 0 -> 0xffff mapping.
+ * The reply's ICMP checksum is computed from the data itself, never from the request's checksum field: a
+ * request accepted because rx checking is off, or one with a bad checksum, still yields the bytes
+ * fill_checksum would write.
+ *
+ * WRITTEN.  Set when ANSWERED and frame_len <= cap: all frame_len bytes go to d_dst[dst_offset ..].
+ * Otherwise nothing is stored for the record; frame_len and head_len are still reported for an ANSWERED
+ * record that does not fit.  THE DATA COPY DOES NOT WAIT FOR THE VERDICT, as in smol_csum_batch_verify_copy.
+ *
+ * SEND = WRITTEN && (status & SMOL_ST_ACCEPT).  The caller transmits a slot only when SEND is set.
+ *
+ * Writes.  No byte of d_dst outside [dst_offset, dst_offset + frame_len) of a WRITTEN record is written and
+ * no byte of d_dst is read: edges and the head go out byte-masked, so slots may lie back to back at any
+ * alignment.  Slots must not overlap each other or the batch.  d_buf is only read.
+ *
+ * Resources.  No context scratch, no event, no allocation; stream-ordered on `stream`, graph-capturable, and
+ * calls on different streams are independent (also on one context).
+ *
+ * SMOL_EINVAL: NULL ctx, bad caps, a non-zero cfg->reserved, NULL d_dst / d_slots / d_status / d_echo with
+ * n > 0, d_slots not 16-byte aligned, d_echo not 8-byte aligned.  SMOL_ERANGE: as verify.  n == 0 returns
+ * SMOL_OK and launches nothing.  Not covered: the 6LoWPAN NHC entry points and IPv4 fragment groups.
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive, as verify_tcp_assemble was). */
+int smol_csum_batch_verify_echo_reply(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
+                                      const smol_checksum_caps_t* caps, const smol_csum_echo_cfg_t* cfg,
+                                      uint8_t* d_dst, const smol_csum_slot_t* d_slots,
+                                      uint8_t* d_status, smol_csum_echo_t* d_echo, void* stream);
 
 /* ---- 4. 6LoWPAN next-header-compressed UDP (RFC 6282 §4.3) ------------------------------- */
 

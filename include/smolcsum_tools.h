@@ -204,6 +204,7 @@ const char* smol_csum_tool_kernel_name(const smol_csum_ctx_t* ctx, int op, int h
  * G 64, U its chunks per lane and step); 12 = fragcut_kernel (smol_csum_batch_fragment_emit: the same);
  * 13 = tcpcut_kernel (smol_csum_batch_tcp_segment_emit: the same);
  * 14 = tcpasm_kernel (smol_csum_batch_verify_tcp_assemble: the same);
+ * 15 = echo_kernel (smol_csum_batch_verify_echo_reply: variant 0, G and U its launch shape);
  * 0 before the first launch.  The fragment kernels of emit_frag /
  * verify_frag record nothing. */
 uint32_t smol_csum_tool_last_launch(void);

@@ -34,7 +34,8 @@ ABI_SYMBOLS = [
     "smol_csum_batch_verify_copy",
     "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
     "smol_csum_batch_verify_frag", "smol_csum_batch_verify_reassemble", "smol_csum_batch_fragment_emit",
-    "smol_csum_batch_tcp_segment_emit", "smol_csum_batch_verify_tcp_assemble", "smol_csum_batch_nhc_udp_emit",
+    "smol_csum_batch_tcp_segment_emit", "smol_csum_batch_verify_tcp_assemble", "smol_csum_batch_verify_echo_reply",
+    "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
 ]
 TOOL_SYMBOLS = [
@@ -230,6 +231,26 @@ class TcpFlowC(ctypes.Structure):
     ]
 
 
+class EchoCfgC(ctypes.Structure):
+    """smol_csum_echo_cfg_t: what the responder knows of the interface (smol_csum_batch_verify_echo_reply)."""
+
+    _fields_ = [
+        ("bcast_v4", ctypes.c_uint8 * 4),
+        ("reserved", ctypes.c_uint8 * 4),
+    ]
+
+
+class EchoC(ctypes.Structure):
+    """smol_csum_echo_t: one record's outcome (smol_csum_batch_verify_echo_reply)."""
+
+    _fields_ = [
+        ("frame_len", ctypes.c_uint32),
+        ("data_off", ctypes.c_uint16),
+        ("head_len", ctypes.c_uint8),
+        ("flags", ctypes.c_uint8),
+    ]
+
+
 _LIBS = {}
 
 
@@ -300,6 +321,10 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.smol_csum_batch_verify_tcp_assemble.argtypes = [vp, vp, ctypes.POINTER(BatchC), vp, u64, ctypes.POINTER(Caps),
                                                           vp, vp, vp, vp, vp, vp]
         L.smol_csum_batch_verify_tcp_assemble.restype = i32
+    if hasattr(L, "smol_csum_batch_verify_echo_reply"):
+        L.smol_csum_batch_verify_echo_reply.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps),
+                                                        ctypes.POINTER(EchoCfgC), vp, vp, vp, vp, vp]
+        L.smol_csum_batch_verify_echo_reply.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []

@@ -229,6 +229,11 @@ inline int vcopy_shape(uint32_t len, bool has_desc) {
     return auto_shape(len, false, kWalkEmitDesc);
 }
 
+// ---- verify_echo_reply (smol_csum_batch_verify_echo_reply) -----------------------------------------
+// One kernel outside the registry (csum_echo.hip), vcopy_kernel's form: it takes verify_copy's shapes (8 x 7
+// over descriptors, auto_shape over fixed strides; tools/exp_echo_reply.py times the call as a whole).
+inline int echo_shape(uint32_t len, bool has_desc) { return vcopy_shape(len, has_desc); }
+
 inline Pick pick_kernel(const PickCtx& ctx, int mode, const smol_csum_batch_t* b, const KParams& p) {
     const bool has_desc = b->desc != nullptr;
     const bool nhc = p.addrs != nullptr;

@@ -257,10 +257,11 @@ __device__ inline uint64_t logical_block(uint32_t xcd_remap) {
 // KERN_FRAGCUT: smol_csum_batch_fragment_emit's kernel (the same).
 // KERN_TCPCUT: smol_csum_batch_tcp_segment_emit's kernel (the same).
 // KERN_TCPASM: smol_csum_batch_verify_tcp_assemble's kernel (the same).
+// KERN_ECHO: smol_csum_batch_verify_echo_reply's kernel (no registry row; variant 0, G and U its launch shape).
 enum {
     KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6,
     KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9, KERN_VCOPY = 10,
-    KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12, KERN_TCPCUT = 13, KERN_TCPASM = 14
+    KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12, KERN_TCPCUT = 13, KERN_TCPASM = 14, KERN_ECHO = 15
 };
 inline std::atomic<uint32_t> g_last_launch{0};
 inline void note_launch(uint32_t kern, uint32_t var, uint32_t g, uint32_t u) {
@@ -392,6 +393,17 @@ struct TcpAsmArgs {
 // max_blocks: the grid cap (smol_csum_tool_set_max_blocks: a few workgroups walk many groups).
 hipError_t launch_tcpasm(const KParams& p, const smol_csum_frag_group_t* groups, uint64_t ngroups,
                          const TcpAsmArgs& v, uint32_t max_blocks, hipStream_t s);
+// verify_echo_reply (smol_csum_batch_verify_echo_reply, csum_echo.hip): verify's status bytes, and for every
+// ICMP echo request that the wire-level address rule answers (csum_echo.h) the whole reply frame written to
+// the record's slot of `dst` in the same pass: fresh head, the request's data, both checksums filled.  Outside
+// the variant registry.
+struct EchoArgs {
+    uint8_t* dst;
+    const smol_csum_slot_t* slots;  // one 16-B entry per record (input)
+    smol_csum_echo_t* echo;         // one 8-B entry per record (output)
+    uint32_t bcast_v4;              // smol_csum_echo_cfg_t.bcast_v4 as a big-endian word (0: none)
+};
+hipError_t launch_echo(int shape, const KParams& p, const EchoArgs& v, uint32_t max_blocks, hipStream_t s);
 hipError_t launch_stream_read(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t max_blocks,
                               hipStream_t s);
 hipError_t launch_field_probe(uint8_t* buf, uint64_t bytes, uint64_t stride, uint32_t f1, uint32_t f2,

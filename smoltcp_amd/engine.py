@@ -16,8 +16,8 @@ from typing import Optional
 import numpy as np
 
 from . import _lib
-from ._lib import (NO_FIELD, BatchC, Caps, DgramC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, TcpFlowC, TcpOutC, TcpPlanC,
-                   TcpSegC, TcpWinC, check, lib)
+from ._lib import (NO_FIELD, BatchC, Caps, DgramC, EchoC, EchoCfgC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, TcpFlowC,
+                   TcpOutC, TcpPlanC, TcpSegC, TcpWinC, check, lib)
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -89,6 +89,10 @@ TCPFLOW_DTYPE = np.dtype([("contig_len", "<u4"), ("counted", "<u4"), ("redeliver
 assert TCPFLOW_DTYPE.itemsize == 16 == ctypes.sizeof(TcpFlowC)
 MAX_FLOW_SEGMENTS = 256
 SEG_TCP, SEG_IN_WINDOW, SEG_COPIED, SEG_REDELIVERED = 0x01, 0x02, 0x04, 0x08  # SMOL_SEG_*
+# smol_csum_echo_t: one record's outcome (smol_csum_batch_verify_echo_reply)
+ECHO_DTYPE = np.dtype([("frame_len", "<u4"), ("data_off", "<u2"), ("head_len", "u1"), ("flags", "u1")])
+assert ECHO_DTYPE.itemsize == 8 == ctypes.sizeof(EchoC)
+ECHO_REQUEST, ECHO_ANSWERED, ECHO_WRITTEN, ECHO_SEND, ECHO_HOST = 0x01, 0x02, 0x04, 0x08, 0x10  # SMOL_ECHO_*
 
 
 def make_slots(dst_offsets, caps) -> np.ndarray:
@@ -550,6 +554,37 @@ class ChecksumEngine:
               "smol_csum_batch_verify_copy")
         return status, spans
 
+    def verify_echo_reply(self, buf, batch: Batch, dst, slots, caps=None, cfg=None, status=None, echo=None, stream=None):
+        """Verify, and in the same pass write the reply to every ICMPv4 / ICMPv6 echo request the wire-level
+        address rule answers to the record's slot of `dst`: fresh Ethernet / IP / ICMP head, the request's
+        data, both checksums filled (smol_csum_batch_verify_echo_reply).  `slots`: a device uint8 tensor of n
+        smol_csum_slot_t (see make_slots); `dst`: the destination uint8 device tensor, written only inside
+        the written frames; `cfg`: None, or the interface's directed-broadcast address as 4 bytes.  Returns
+        (status, echo): verify's status bytes and an n x 8 uint8 device tensor of smol_csum_echo_t (view its
+        host copy as ECHO_DTYPE).  The copy does not wait for the verdict: transmit a slot only when its
+        entry has ECHO_SEND; ECHO_HOST marks the requests the host has to answer itself."""
+        import torch
+
+        self._check_buf(buf, batch)
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert slots.is_cuda and slots.is_contiguous() and slots.numel() * slots.dtype.itemsize >= 16 * batch.n
+        if status is None:
+            status = torch.empty(batch.n, dtype=torch.uint8, device=buf.device)
+        if echo is None:
+            echo = torch.empty((batch.n, 8), dtype=torch.uint8, device=buf.device)
+        assert echo.is_cuda and echo.is_contiguous() and echo.numel() * echo.dtype.itemsize >= 8 * batch.n
+        b = batch.c()
+        c = _caps(caps)
+        cfg_c = None
+        if cfg is not None:
+            cfg_c = cfg if isinstance(cfg, EchoCfgC) else EchoCfgC((ctypes.c_uint8 * 4)(*bytes(cfg)), (ctypes.c_uint8 * 4)())
+        check(self._L.smol_csum_batch_verify_echo_reply(self._h, buf.data_ptr(), ctypes.byref(b), ctypes.byref(c),
+                                                      ctypes.byref(cfg_c) if cfg_c is not None else None,
+                                                      dst.data_ptr(), slots.data_ptr(), status.data_ptr(),
+                                                      echo.data_ptr(), self._stream(stream)),
+              "smol_csum_batch_verify_echo_reply")
+        return status, echo
+
     # ---- tooling ----
     def synth(self, buf, batch: Batch, profile: int, seed: int, stream=None):
         self._check_buf(buf, batch)
@@ -660,13 +695,13 @@ class ChecksumEngine:
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
         "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
-        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel" | verify_tcp_assemble's "tcpasm_kernel", "variant": VAR, "G":
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel" | verify_tcp_assemble's "tcpasm_kernel" | verify_echo_reply's "echo", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
                  6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel",
-                 11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel", 14: "tcpasm_kernel"}
+                 11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel", 14: "tcpasm_kernel", 15: "echo"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

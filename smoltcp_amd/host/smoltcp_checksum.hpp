@@ -311,6 +311,22 @@ public:
               "smol_csum_batch_verify_tcp_assemble");
     }
 
+    // verify, and in the same pass the reply to every ICMPv4 / ICMPv6 echo request the wire-level address rule
+    // answers written to d_dst at d_slots[i]: fresh Ethernet / IP / ICMP head, the request's data, both
+    // checksums filled under `caps` (the iface's responder: process_icmpv4 src/iface/interface/ipv4.rs:320-371,
+    // process_icmpv6 ipv6.rs:399-416, icmpv4_reply / icmpv6_reply and the reply's dispatch).  d_echo[i] = the
+    // reply's length, the data's offset and SMOL_ECHO_* flags; cfg: nullptr, or the iface's directed-broadcast
+    // address.  Transmit a slot only when its entry has SMOL_ECHO_SEND; SMOL_ECHO_HOST marks the requests the
+    // host answers itself.  The copy waits for no verdict; d_buf is only read.
+    void verify_echo_reply(const uint8_t* d_buf, const Batch& b, uint8_t* d_dst, const smol_csum_slot_t* d_slots,
+                           uint8_t* d_status, smol_csum_echo_t* d_echo, const smol_csum_echo_cfg_t* cfg = nullptr,
+                           const smoltcp::phy::ChecksumCapabilities& caps = {}, void* stream = nullptr) {
+        auto bc = b.c();
+        auto cc = caps.c();
+        check(smol_csum_batch_verify_echo_reply(ctx_, d_buf, &bc, &cc, cfg, d_dst, d_slots, d_status, d_echo, stream),
+              "smol_csum_batch_verify_echo_reply");
+    }
+
     // 6LoWPAN NHC UDP (sixlowpan::nhc::UdpNhcRepr::emit / ::parse): every record is a LOWPAN_NHC
     // UDP packet; d_addrs[i] holds record i's IPv6 addresses (IPHC-decompressed).
     void nhc_udp_emit(uint8_t* d_buf, const Batch& b, const smol_ipv6_addr_pair_t* d_addrs,
