@@ -81,7 +81,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((SEGF & (DW
     if (p.desc) {
         if ((uint32_t)wl < cnt) d = *(gcv4)((uint64_t)p.desc + 16 * (rw0 + (uint64_t)wl));
     } else {
-        const uint64_t off = (rw0 + (uint64_t)wl) * p.stride;
+        // lanes past the last record: offset 0 as above (a group without a record still loads its line's head)
+        const uint64_t off = (uint32_t)wl < cnt ? (rw0 + (uint64_t)wl) * p.stride : 0ull;
         d = u32x4{(uint32_t)off, (uint32_t)(off >> 32), (uint32_t)wl < cnt ? p.len : 0u, 0u};
     }
     constexpr bool LITE = (SEGF & DW_LITE) != 0 && MODE == MODE_EMIT;

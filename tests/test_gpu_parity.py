@@ -690,8 +690,10 @@ def _expected_launch(variant, op, has_desc):
     return ("csum_kernel", variant)
 
 
-@pytest.mark.parametrize("variant", [0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 12, 13, 14, 19, 23, 24, 25, 26, 27, 28, 29, 37, 38,
-                                     39, 62])
+FIXED_STRIDE_VARIANTS = [0, 1, 2, 3, 4, 5, 6, 7, 9, 10, 12, 13, 14, 19, 23, 24, 25, 26, 27, 28, 29, 37, 38, 39, 62]
+
+
+@pytest.mark.parametrize("variant", FIXED_STRIDE_VARIANTS)
 def test_variants_fixed_stride(eng, variant):
     """The non-default kernel variants (walk: nt + prefetch, nt only; tile: nt, plain loads) against
     the oracle on fixed-stride batches: strides equal to the record length (neighbours share
