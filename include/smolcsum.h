@@ -39,6 +39,9 @@
  *       - smol_csum_batch_verify_echo_reply == verify, and in the same pass the reply to every ICMP echo
  *         request written to a caller-chosen slot, head fresh, data echoed, checksums filled (the
  *         iface's own responder, process_icmpv4 / process_icmpv6 and the dispatch of their reply);
+ *       - smol_csum_batch_verify_unreach_reply == verify, and in the same pass the ICMP error for every
+ *         datagram nobody takes (a closed UDP port, an unhandled protocol or next header) written to a
+ *         caller-chosen slot, both headers fresh, the payload quoted, checksums filled;
  *       - smol_csum_batch_data  == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
@@ -908,6 +911,134 @@ int smol_csum_batch_verify_echo_reply(smol_csum_ctx_t* ctx, const uint8_t* d_buf
                                       const smol_checksum_caps_t* caps, const smol_csum_echo_cfg_t* cfg,
                                       uint8_t* d_dst, const smol_csum_slot_t* d_slots,
                                       uint8_t* d_status, smol_csum_echo_t* d_echo, void* stream);
+
+/* ---- verify_unreach_reply: refused datagrams verified, the ICMP errors written in the same pass ---- */
+
+/* One record's outcome (8 bytes, 8-byte-aligned device array, output): smol_csum_echo_t's layout. */
+typedef struct {
+    uint32_t frame_len; /* the error frame's length; 0 unless SMOL_UNR_ANSWERED                */
+    uint16_t data_off;  /* record-relative offset of the IP payload; 0 unless SMOL_UNR_REFUSED */
+    uint8_t head_len;   /* frame bytes in front of the data; 0 unless ANSWERED                  */
+    uint8_t flags;      /* SMOL_UNR_*                                                           */
+} smol_csum_unreach_t;
+#define SMOL_UNR_REFUSED  0x01u /* the interface answers this record with an ICMP error          */
+#define SMOL_UNR_ANSWERED 0x02u /* the wire-level address rule lets the device write the frame   */
+#define SMOL_UNR_WRITTEN  0x04u /* ANSWERED and frame_len <= cap: the frame is in the slot       */
+#define SMOL_UNR_SEND     0x08u /* WRITTEN and status & SMOL_ST_ACCEPT: transmit the slot        */
+#define SMOL_UNR_HOST     0x10u /* REFUSED, but only the host can build the reply                */
+#define SMOL_UNR_PORT     0x20u /* REFUSED as a UDP datagram to a closed port (else: protocol / next header) */
+
+/* Verify, and write the ICMP error for every datagram of the batch that nobody takes to its slot of d_dst, in
+ * one pass.  The interface's second automatic reply with per-byte work (the first is the echo responder above):
+ *   - a UDP datagram to a port no socket accepts gets Destination Unreachable / Port Unreachable
+ *     (InterfaceInner::process_udp, src/iface/interface/udp.rs:49-77);
+ *   - an IPv4 packet with a protocol the stack does not handle gets Protocol Unreachable
+ *     (src/iface/interface/ipv4.rs:240-250);
+ *   - an IPv6 packet with an unrecognised next header gets Parameter Problem (process_nxt_hdr,
+ *     src/iface/interface/ipv6.rs:352-364).
+ * Each reply quotes a re-emitted copy of the offending IP header and as much of the offending payload as the
+ * minimum MTU allows (icmp_reply_payload_len, src/iface/packet.rs:254-264): 528 bytes over IPv4, 1192 over
+ * IPv6.  The reference reads those bytes twice and sums them twice: UdpRepr::parse sums the datagram,
+ * Icmpv4Repr::emit / Icmpv6Repr::emit copy the slice (src/wire/icmpv4.rs:519-531, src/wire/icmpv6.rs:740-755)
+ * and fill_checksum sums the copy.  Here each record byte is read once.
+ *
+ * d_udp_open (8192-byte device bitmap, nullable, only read): bit (p & 7) of byte (p >> 3) is set when the host
+ * wants UDP datagrams for destination port p itself, because a UDP, DNS or DHCP socket may take them or a raw
+ * socket handles UDP.  A clear bit means no socket accepts the port.  NULL means every UDP datagram is the
+ * host's, so only protocol / next-header errors are answered.  A host with a socket that matches on something
+ * other than the destination port (the DNS socket matches the SOURCE port, src/socket/dns.rs accepts) passes
+ * NULL or sets every bit.
+ * cfg: smol_csum_batch_verify_echo_reply's struct, for its directed-broadcast address; NULL means all zero.
+ *
+ * Status.  d_status[i] is exactly the byte smol_csum_batch_verify writes for the same batch and caps, for
+ * every record.
+ *
+ * REFUSED.  The record is SMOL_KIND_IP or SMOL_KIND_ETH (ethertype 0x0800 / 0x86DD matching the version
+ * nibble, src/iface/interface/ethernet.rs:4-46), carries no SMOL_REC_IPHDR_ONLY (a raw socket handled it:
+ * handled_by_raw_socket, udp.rs:52-54, ipv4.rs:240, ipv6.rs:350), and is one of (io: the IP header's offset):
+ *   IPv4, protocol: the header passes Ipv4Packet::check_len (src/wire/ipv4.rs:241-256), the packet is no
+ *     fragment (MF clear, offset 0: fragments belong to the reassembler, ipv4.rs:110-146) and the protocol is
+ *     none of 1, 2, 6, 17.  ICMPv4 type 3 code 2 (ipv4.rs:240-250).  P = total length - IHL * 4; the data
+ *     starts at io + IHL * 4.
+ *   IPv4, port (sets PORT): the same header conditions, protocol 17, verify's parse marks the record neither
+ *     SMOL_ST_MALFORMED nor SMOL_ST_UNSUPPORTED (UdpPacket::check_len passed, src/wire/udp.rs:57-69, and the
+ *     destination port is not 0, udp.rs:246-248), d_udp_open is not NULL and the destination port's bit is
+ *     clear.  Type 3 code 3 (udp.rs:56-65).
+ *   IPv6, next header: Ipv6Packet::check_len passes (src/wire/ipv6.rs:400-407) and the next header is none of
+ *     0, 6, 17, 58.  ICMPv6 type 4 code 1 with pointer = 40 (ipv6_repr.buffer_len(), as ipv6.rs:359 writes
+ *     it).  P = the payload length; the data starts at io + 40.
+ *   IPv6, port (sets PORT): next header 17 directly, with the UDP conditions above.  ICMPv6 type 1 code 4
+ *     (udp.rs:67-76).
+ *   IPv6 with a leading Hop-by-Hop header: when verify does not mark it MALFORMED (process_hopbyhop,
+ *     ipv6.rs:263-319) and the header behind it meets one of the two IPv6 rules (a second Hop-by-Hop header
+ *     there is an unrecognised next header to process_nxt_hdr), the record is REFUSED | HOST (REFUSED alone
+ *     when its source is not unicast, as below), data_off = io + 40, and nothing is written: the reference quotes the next-header-0 header in front of the post-option
+ *     payload (ipv6.rs:315-318), and its option-triggered Parameter Problem (ipv6.rs:268-280) is a third
+ *     message.  Both stay with the host.
+ * TCP (the RST is header-only work), ICMP, IGMP, fragments, malformed records, SMOL_KIND_RAW, non-IP
+ * ethertypes and UDP datagrams to an open port get an all-zero entry, and nothing is stored for them.
+ *
+ * Address rule, with nonuni4 / nonuni6 / the MAC test of smol_csum_batch_verify_echo_reply:
+ *   IPv4 (icmpv4_reply, ipv4.rs:394-414): ANSWERED iff neither source nor destination is nonuni4.  Otherwise
+ *     the entry has neither ANSWERED nor HOST: the reference answers broadcasts for echo replies only.
+ *   IPv6 (process_ipv6, ipv6.rs:198, and icmpv6_reply, ipv6.rs:538-563): nonuni6(src): neither.  A unicast
+ *     destination: ANSWERED.  A multicast or unspecified one: HOST (get_source_address_ipv6).
+ *   SMOL_KIND_ETH: both MACs must be unicast, else ANSWERED becomes HOST.
+ * ANSWERED and HOST exclude each other, and both imply REFUSED.
+ *
+ * Data.  dlen = min(P, 528) over IPv4 and min(P, 1192) over IPv6: icmp_reply_payload_len(len, MIN_MTU, 20 |
+ * 40).  The data is record bytes [data_off, data_off + dlen): the first bytes of the IP payload, not of the
+ * UDP span.  When the UDP length field is shorter than P, the bytes past it are copied and summed into the
+ * reply but are no part of the verdict, as in the reference's two passes (ip_payload[0..payload_len],
+ * udp.rs:62).  Ethernet padding past the IP length is never read into either.
+ *
+ * The frame (ANSWERED records only).  head_len is 48 / 62 (IPv4: SMOL_KIND_IP / SMOL_KIND_ETH) or 88 / 102
+ * (IPv6); frame_len = head_len + dlen, at most 590 and 1294 (576 and 1280 bytes of IP: the sizes
+ * test_icmp_reply_size pins, src/iface/interface/tests/ipv4.rs:1390, ipv6.rs:1141).
+ *   Ethernet: the MACs swapped, the request's ethertype.
+ *   Outer IPv4 as Ipv4Repr::emit (src/wire/ipv4.rs:584-612): 45 00, total length 48 + dlen, ident 0, 40 00,
+ *     TTL 64, protocol 1, checksum, source = the request's destination, destination = the request's source.
+ *   Outer IPv6 (Ipv6Repr::emit, src/wire/ipv6.rs:631-638): 60 00 00 00, payload length 48 + dlen, next header
+ *     58, hop limit 64, the addresses swapped.
+ *   ICMP: type, code, checksum, then four bytes: 0 for the Destination Unreachable forms (the reference leaves
+ *     them as its token buffer held them, Icmpv4Repr::emit icmpv4.rs:519-531 writes none of them; 0 is what a
+ *     fresh buffer gives), 00 00 00 28 for Parameter Problem (set_param_problem_ptr, icmpv6.rs:796).
+ *   The quoted header, emitted again from the parsed repr, not copied (header.emit, icmpv4.rs:527-528,
+ *     icmpv6.rs:745-746).  IPv4: 20 bytes: 45 00, total length 20 + P (the full P, not dlen), ident 0, 40 00,
+ *     the request's TTL and protocol, checksum, the request's source and destination unswapped; the request's
+ *     DSCP / ECN, ident, flags and options are not carried.  IPv6: 40 bytes: 60 00 00 00, payload length P, the
+ *     request's next header and hop limit, its addresses unswapped; traffic class and flow label are not
+ *     carried.
+ *   Then the data.
+ * Checksums are filled as smol_csum_batch_emit fills them on that frame under `caps`: both IPv4 header
+ * checksums under caps.ipv4 tx (Icmpv4Repr::emit hands the quoted header the same caps, icmpv4.rs:527-528),
+ * else 0; the ICMPv4 checksum over the message with the quoted header's final checksum, under caps.icmpv4; the
+ * ICMPv6 checksum with its pseudo-header, under caps.icmpv6.  None of them is derived from a checksum field of
+ * the request.
+ *
+ * WRITTEN.  Set when ANSWERED and frame_len <= cap: all frame_len bytes go to d_dst[dst_offset ..].  Otherwise
+ * nothing is stored for the record; the lengths are still reported.  THE COPY DOES NOT WAIT FOR THE VERDICT.
+ *
+ * SEND = WRITTEN && (status & SMOL_ST_ACCEPT).  The reference replies only after Ipv4Repr::parse and
+ * UdpRepr::parse passed their checksum gates; for an unsupported protocol ACCEPT reduces to the IPv4 gate.
+ *
+ * Writes.  No byte of d_dst outside [dst_offset, dst_offset + frame_len) of a WRITTEN record is written and
+ * no byte of d_dst is read: edges and the head go out byte-masked, so slots may lie back to back at any
+ * alignment.  Slots must not overlap each other or the batch.  d_buf and d_udp_open are only read.
+ *
+ * Resources.  No context scratch, no event, no allocation; stream-ordered on `stream`, graph-capturable, and
+ * calls on different streams are independent (also on one context).
+ *
+ * SMOL_EINVAL: NULL ctx, bad caps, a non-zero cfg->reserved, NULL d_dst / d_slots / d_status / d_unr with
+ * n > 0, d_slots not 16-byte aligned, d_unr not 8-byte aligned.  SMOL_ERANGE: as verify.  n == 0 returns
+ * SMOL_OK and launches nothing.  Not covered: the 6LoWPAN NHC entry points and IPv4 fragment groups.
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive, as verify_echo_reply was). */
+int smol_csum_batch_verify_unreach_reply(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
+                                         const smol_checksum_caps_t* caps, const smol_csum_echo_cfg_t* cfg,
+                                         const uint8_t* d_udp_open, /* 8192-byte device bitmap, nullable */
+                                         uint8_t* d_dst, const smol_csum_slot_t* d_slots,
+                                         uint8_t* d_status, smol_csum_unreach_t* d_unr, void* stream);
 
 /* ---- 4. 6LoWPAN next-header-compressed UDP (RFC 6282 §4.3) ------------------------------- */
 

@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
     "smol_csum_batch_verify_frag", "smol_csum_batch_verify_reassemble", "smol_csum_batch_fragment_emit",
     "smol_csum_batch_tcp_segment_emit", "smol_csum_batch_verify_tcp_assemble", "smol_csum_batch_verify_echo_reply",
-    "smol_csum_batch_nhc_udp_emit",
+    "smol_csum_batch_verify_unreach_reply", "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
 ]
 TOOL_SYMBOLS = [
@@ -251,6 +251,17 @@ class EchoC(ctypes.Structure):
     ]
 
 
+class UnreachC(ctypes.Structure):
+    """smol_csum_unreach_t: one record's outcome (smol_csum_batch_verify_unreach_reply)."""
+
+    _fields_ = [
+        ("frame_len", ctypes.c_uint32),
+        ("data_off", ctypes.c_uint16),
+        ("head_len", ctypes.c_uint8),
+        ("flags", ctypes.c_uint8),
+    ]
+
+
 _LIBS = {}
 
 
@@ -325,6 +336,10 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.smol_csum_batch_verify_echo_reply.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps),
                                                         ctypes.POINTER(EchoCfgC), vp, vp, vp, vp, vp]
         L.smol_csum_batch_verify_echo_reply.restype = i32
+    if hasattr(L, "smol_csum_batch_verify_unreach_reply"):
+        L.smol_csum_batch_verify_unreach_reply.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps),
+                                                           ctypes.POINTER(EchoCfgC), vp, vp, vp, vp, vp, vp]
+        L.smol_csum_batch_verify_unreach_reply.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []

@@ -404,6 +404,34 @@ int smol_csum_batch_verify_echo_reply(smol_csum_ctx_t* ctx, const uint8_t* d_buf
     });
 }
 
+// Verify with the ICMP errors for the batch's refused datagrams written in the same pass (include/smolcsum.h).
+// Uses none of the context's scratch or events, so calls on different streams are independent.
+int smol_csum_batch_verify_unreach_reply(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
+                                         const smol_checksum_caps_t* caps, const smol_csum_echo_cfg_t* cfg,
+                                         const uint8_t* d_udp_open, uint8_t* d_dst, const smol_csum_slot_t* d_slots,
+                                         uint8_t* d_status, smol_csum_unreach_t* d_unr, void* stream) {
+    int rc;
+    const bool work = begin_call(ctx, caps, b, d_buf, &rc);
+    if (rc != SMOL_OK) return rc;
+    if (cfg && (cfg->reserved[0] | cfg->reserved[1] | cfg->reserved[2] | cfg->reserved[3])) return SMOL_EINVAL;
+    if (!work) return rc;
+    if (!d_dst || !d_slots || !d_status || !d_unr || ((uintptr_t)d_slots & 15u) != 0 || ((uintptr_t)d_unr & 7u) != 0)
+        return SMOL_EINVAL;
+    KParams p = base_params(ctx, d_buf, b, caps);
+    p.status = d_status;
+    const uint32_t bcast = cfg ? (uint32_t)cfg->bcast_v4[0] << 24 | (uint32_t)cfg->bcast_v4[1] << 16 |
+                                     (uint32_t)cfg->bcast_v4[2] << 8 | (uint32_t)cfg->bcast_v4[3]
+                               : 0u;
+    const hipStream_t s = (hipStream_t)stream;
+    const int shape = ctx->shape >= 0 ? ctx->shape : unreach_shape(b->len, b->desc != nullptr);
+    return on_device(ctx, "verify_unreach_reply kernel launch", [&] {
+        return for_chunks(p, ctx->launch_records, [&](uint64_t i0, const KParams& q) {
+            const UnreachArgs v = {d_dst, d_slots + i0, d_unr + i0, d_udp_open, bcast};
+            return launch_unreach(shape, q, v, ctx->max_blocks, s);
+        });
+    });
+}
+
 // ---- IPv4 fragment groups ---------------------------------------------------------------------
 
 static int run_frag(smol_csum_ctx_t* ctx, int mode, uint8_t* d_buf, const smol_csum_batch_t* b,

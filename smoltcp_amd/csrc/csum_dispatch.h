@@ -234,6 +234,11 @@ inline int vcopy_shape(uint32_t len, bool has_desc) {
 // over descriptors, auto_shape over fixed strides; tools/exp_echo_reply.py times the call as a whole).
 inline int echo_shape(uint32_t len, bool has_desc) { return vcopy_shape(len, has_desc); }
 
+// ---- verify_unreach_reply (smol_csum_batch_verify_unreach_reply) -----------------------------------
+// One kernel outside the registry (csum_unreach.hip), echo_kernel's form: verify_copy's shapes again
+// (tools/exp_unreach_reply.py times the call as a whole).
+inline int unreach_shape(uint32_t len, bool has_desc) { return vcopy_shape(len, has_desc); }
+
 inline Pick pick_kernel(const PickCtx& ctx, int mode, const smol_csum_batch_t* b, const KParams& p) {
     const bool has_desc = b->desc != nullptr;
     const bool nhc = p.addrs != nullptr;

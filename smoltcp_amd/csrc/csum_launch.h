@@ -258,10 +258,12 @@ __device__ inline uint64_t logical_block(uint32_t xcd_remap) {
 // KERN_TCPCUT: smol_csum_batch_tcp_segment_emit's kernel (the same).
 // KERN_TCPASM: smol_csum_batch_verify_tcp_assemble's kernel (the same).
 // KERN_ECHO: smol_csum_batch_verify_echo_reply's kernel (no registry row; variant 0, G and U its launch shape).
+// KERN_UNREACH: smol_csum_batch_verify_unreach_reply's kernel (the same).
 enum {
     KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6,
     KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9, KERN_VCOPY = 10,
-    KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12, KERN_TCPCUT = 13, KERN_TCPASM = 14, KERN_ECHO = 15
+    KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12, KERN_TCPCUT = 13, KERN_TCPASM = 14, KERN_ECHO = 15,
+    KERN_UNREACH = 16
 };
 inline std::atomic<uint32_t> g_last_launch{0};
 inline void note_launch(uint32_t kern, uint32_t var, uint32_t g, uint32_t u) {
@@ -404,6 +406,18 @@ struct EchoArgs {
     uint32_t bcast_v4;              // smol_csum_echo_cfg_t.bcast_v4 as a big-endian word (0: none)
 };
 hipError_t launch_echo(int shape, const KParams& p, const EchoArgs& v, uint32_t max_blocks, hipStream_t s);
+// verify_unreach_reply (smol_csum_batch_verify_unreach_reply, csum_unreach.hip): verify's status bytes, and for
+// every datagram nobody takes that the wire-level address rule answers (csum_unreach.h) the whole ICMP error
+// frame written to the record's slot of `dst` in the same pass: both headers fresh, the payload's first bytes
+// quoted, every checksum filled.  Outside the variant registry.
+struct UnreachArgs {
+    uint8_t* dst;
+    const smol_csum_slot_t* slots;  // one 16-B entry per record (input)
+    smol_csum_unreach_t* unr;       // one 8-B entry per record (output)
+    const uint8_t* udp_open;        // the 8192-B port map (nullptr: no UDP datagram is refused)
+    uint32_t bcast_v4;              // smol_csum_echo_cfg_t.bcast_v4 as a big-endian word (0: none)
+};
+hipError_t launch_unreach(int shape, const KParams& p, const UnreachArgs& v, uint32_t max_blocks, hipStream_t s);
 hipError_t launch_stream_read(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t max_blocks,
                               hipStream_t s);
 hipError_t launch_field_probe(uint8_t* buf, uint64_t bytes, uint64_t stride, uint32_t f1, uint32_t f2,

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (NO_FIELD, BatchC, Caps, DgramC, EchoC, EchoCfgC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, TcpFlowC,
-                   TcpOutC, TcpPlanC, TcpSegC, TcpWinC, check, lib)
+                   TcpOutC, TcpPlanC, TcpSegC, TcpWinC, UnreachC, check, lib)
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -93,6 +93,22 @@ SEG_TCP, SEG_IN_WINDOW, SEG_COPIED, SEG_REDELIVERED = 0x01, 0x02, 0x04, 0x08  # 
 ECHO_DTYPE = np.dtype([("frame_len", "<u4"), ("data_off", "<u2"), ("head_len", "u1"), ("flags", "u1")])
 assert ECHO_DTYPE.itemsize == 8 == ctypes.sizeof(EchoC)
 ECHO_REQUEST, ECHO_ANSWERED, ECHO_WRITTEN, ECHO_SEND, ECHO_HOST = 0x01, 0x02, 0x04, 0x08, 0x10  # SMOL_ECHO_*
+# smol_csum_unreach_t: one record's outcome (smol_csum_batch_verify_unreach_reply)
+UNR_DTYPE = np.dtype([("frame_len", "<u4"), ("data_off", "<u2"), ("head_len", "u1"), ("flags", "u1")])
+assert UNR_DTYPE.itemsize == 8 == ctypes.sizeof(UnreachC)
+UNR_REFUSED, UNR_ANSWERED, UNR_WRITTEN, UNR_SEND, UNR_HOST, UNR_PORT = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20  # SMOL_UNR_*
+
+
+def make_port_map(open_ports) -> np.ndarray:
+    """The 8192-byte bitmap smol_csum_batch_verify_unreach_reply takes as d_udp_open (copy it to the device): bit
+    p & 7 of byte p >> 3 set for every UDP destination port p of `open_ports`, the ports the host wants the
+    datagrams of itself."""
+    m = np.zeros(8192, dtype=np.uint8)
+    for p in open_ports:
+        p = int(p)
+        assert 0 <= p <= 0xFFFF
+        m[p >> 3] |= 1 << (p & 7)
+    return m
 
 
 def make_slots(dst_offsets, caps) -> np.ndarray:
@@ -585,6 +601,43 @@ class ChecksumEngine:
               "smol_csum_batch_verify_echo_reply")
         return status, echo
 
+    def verify_unreach_reply(self, buf, batch: Batch, dst, slots, udp_open=None, caps=None, cfg=None, status=None, unr=None,
+                             stream=None):
+        """Verify, and in the same pass write the ICMP error for every datagram nobody takes (a UDP datagram
+        to a closed port, an IPv4 protocol or IPv6 next header the stack does not handle) that the wire-level
+        address rule answers to the record's slot of `dst`: fresh Ethernet / IP / ICMP head, the offending IP
+        header emitted again, the first 528 / 1192 bytes of its payload, every checksum filled
+        (smol_csum_batch_verify_unreach_reply).  `udp_open`: None (no UDP datagram is refused), or the 8192-byte
+        device bitmap of make_port_map; a host with a socket that matches on something other than the
+        destination port (the DNS socket) passes None or sets every bit.  `slots`, `dst`, `cfg`: as
+        verify_echo_reply.  Returns (status, unr): verify's status bytes and an n x 8 uint8 device tensor of
+        smol_csum_unreach_t (view its host copy as UNR_DTYPE).  The copy does not wait for the verdict:
+        transmit a slot only when its entry has UNR_SEND; UNR_HOST marks the replies the host has to build."""
+        import torch
+
+        self._check_buf(buf, batch)
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert slots.is_cuda and slots.is_contiguous() and slots.numel() * slots.dtype.itemsize >= 16 * batch.n
+        if udp_open is not None:
+            assert udp_open.is_cuda and udp_open.is_contiguous() and udp_open.dtype.itemsize == 1 and udp_open.numel() >= 8192
+        if status is None:
+            status = torch.empty(batch.n, dtype=torch.uint8, device=buf.device)
+        if unr is None:
+            unr = torch.empty((batch.n, 8), dtype=torch.uint8, device=buf.device)
+        assert unr.is_cuda and unr.is_contiguous() and unr.numel() * unr.dtype.itemsize >= 8 * batch.n
+        b = batch.c()
+        c = _caps(caps)
+        cfg_c = None
+        if cfg is not None:
+            cfg_c = cfg if isinstance(cfg, EchoCfgC) else EchoCfgC((ctypes.c_uint8 * 4)(*bytes(cfg)), (ctypes.c_uint8 * 4)())
+        check(self._L.smol_csum_batch_verify_unreach_reply(self._h, buf.data_ptr(), ctypes.byref(b), ctypes.byref(c),
+                                                         ctypes.byref(cfg_c) if cfg_c is not None else None,
+                                                         udp_open.data_ptr() if udp_open is not None else None,
+                                                         dst.data_ptr(), slots.data_ptr(), status.data_ptr(),
+                                                         unr.data_ptr(), self._stream(stream)),
+              "smol_csum_batch_verify_unreach_reply")
+        return status, unr
+
     # ---- tooling ----
     def synth(self, buf, batch: Batch, profile: int, seed: int, stream=None):
         self._check_buf(buf, batch)
@@ -695,13 +748,13 @@ class ChecksumEngine:
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
         "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
-        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel" | verify_tcp_assemble's "tcpasm_kernel" | verify_echo_reply's "echo", "variant": VAR, "G":
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel" | verify_tcp_assemble's "tcpasm_kernel" | verify_echo_reply's "echo" | verify_unreach_reply's "unreach", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
                  6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel",
-                 11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel", 14: "tcpasm_kernel", 15: "echo"}
+                 11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel", 14: "tcpasm_kernel", 15: "echo", 16: "unreach"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

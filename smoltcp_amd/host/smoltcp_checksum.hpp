@@ -327,6 +327,27 @@ public:
               "smol_csum_batch_verify_echo_reply");
     }
 
+    // verify, and in the same pass the ICMP error for every datagram nobody takes that the wire-level address
+    // rule answers written to d_dst at d_slots[i]: Destination Unreachable / Port Unreachable for a UDP datagram
+    // whose destination port's bit in d_udp_open is clear (process_udp, src/iface/interface/udp.rs:49-77),
+    // Protocol Unreachable for an unhandled IPv4 protocol (ipv4.rs:240-250), Parameter Problem for an
+    // unrecognised IPv6 next header (process_nxt_hdr ipv6.rs:352-364); both headers fresh, the first 528 / 1192
+    // payload bytes quoted, every checksum filled under `caps`.  d_udp_open: nullptr (no UDP datagram is
+    // refused), or 8192 bytes, bit p & 7 of byte p >> 3 set for every port the host wants itself; a host with a
+    // socket that matches on something other than the destination port (the DNS socket) passes nullptr or sets
+    // every bit.  Transmit a slot only when its entry has SMOL_UNR_SEND; SMOL_UNR_HOST marks the replies the
+    // host builds itself.  The copy waits for no verdict; d_buf and d_udp_open are only read.
+    void verify_unreach_reply(const uint8_t* d_buf, const Batch& b, const uint8_t* d_udp_open, uint8_t* d_dst,
+                              const smol_csum_slot_t* d_slots, uint8_t* d_status, smol_csum_unreach_t* d_unr,
+                              const smol_csum_echo_cfg_t* cfg = nullptr,
+                              const smoltcp::phy::ChecksumCapabilities& caps = {}, void* stream = nullptr) {
+        auto bc = b.c();
+        auto cc = caps.c();
+        check(smol_csum_batch_verify_unreach_reply(ctx_, d_buf, &bc, &cc, cfg, d_udp_open, d_dst, d_slots, d_status, d_unr,
+                                                   stream),
+              "smol_csum_batch_verify_unreach_reply");
+    }
+
     // 6LoWPAN NHC UDP (sixlowpan::nhc::UdpNhcRepr::emit / ::parse): every record is a LOWPAN_NHC
     // UDP packet; d_addrs[i] holds record i's IPv6 addresses (IPHC-decompressed).
     void nhc_udp_emit(uint8_t* d_buf, const Batch& b, const smol_ipv6_addr_pair_t* d_addrs,
