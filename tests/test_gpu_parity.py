@@ -746,6 +746,7 @@ WIDE_KERNELS = {
     46: ("xwalk_kernel", 16257),
     47: ("xwalk_kernel", 16257),
     57: ("xwalk_kernel", 16257),
+    89: ("xwalk_kernel", 16257),  # the verify table's 'h': lanes 0-3 of each record's first load cached (emit: 57's form)
     101: ("xwalk_kernel", 16257),  # 57 with write-through segment stores (late round 6)
     107: ("xwalk_kernel", 16257),  # 89 in 512-thread workgroups (verify; emit 101)
     113: ("xwalk_kernel", 16257),  # two tiles per workgroup (89 / 101)
