@@ -42,6 +42,9 @@
  *       - smol_csum_batch_verify_unreach_reply == verify, and in the same pass the ICMP error for every
  *         datagram nobody takes (a closed UDP port, an unhandled protocol or next header) written to a
  *         caller-chosen slot, both headers fresh, the payload quoted, checksums filled;
+ *       - smol_csum_batch_verify_udp_enqueue == verify over the frames of UDP sockets, and in the same
+ *         pass each datagram's payload put where the socket's PacketBuffer::enqueue places it, metadata
+ *         entries written (UdpSocket::process' rx_buffer.enqueue and copy_from_slice);
  *       - smol_csum_batch_data  == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
@@ -1039,6 +1042,166 @@ int smol_csum_batch_verify_unreach_reply(smol_csum_ctx_t* ctx, const uint8_t* d_
                                          const uint8_t* d_udp_open, /* 8192-byte device bitmap, nullable */
                                          uint8_t* d_dst, const smol_csum_slot_t* d_slots,
                                          uint8_t* d_status, smol_csum_unreach_t* d_unr, void* stream);
+
+/* ---- verify_udp_enqueue: datagrams verified into their sockets' receive buffers ---------- */
+
+#define SMOL_MAX_SOCKET_DGRAMS 256u
+
+/* One UDP socket's receive buffer before the poll (48 bytes, 16-byte-aligned device array, input; one per
+ * GROUP): the two RingBuffers of its PacketBuffer (src/storage/packet_buffer.rs:43-46). */
+typedef struct {
+    uint64_t dst_offset;   /* byte offset of the payload ring's storage in d_dst (any alignment)  */
+    uint64_t meta_first;   /* index of the metadata ring's first entry in d_meta                  */
+    uint32_t payload_cap;  /* payload_ring.capacity()                                             */
+    uint32_t payload_read; /* payload_ring.read_at                                                */
+    uint32_t payload_len;  /* payload_ring.len()                                                  */
+    uint32_t meta_cap;     /* metadata_ring.capacity()                                            */
+    uint32_t meta_read;    /* metadata_ring.read_at                                               */
+    uint32_t meta_len;     /* metadata_ring.len()                                                 */
+    uint16_t port;         /* the socket's bound port (endpoint.port)                             */
+    uint16_t reserved[3];  /* must be 0                                                           */
+} smol_csum_udpsock_t;
+
+/* One metadata entry (48 bytes, 16-byte-aligned device array d_meta, output): PacketMetadata<UdpMetadata>. */
+typedef struct {
+    uint32_t size;           /* payload bytes (PADDING: the bytes skipped at the ring's end)           */
+    uint32_t record;         /* batch index of the datagram: the stand-in for PacketMeta               */
+    uint16_t src_port;       /* endpoint.port                                                          */
+    uint8_t family;          /* 4 or 6                                                                 */
+    uint8_t kind;            /* SMOL_UMETA_*                                                           */
+    uint8_t reserved[4];     /* 0                                                                      */
+    uint8_t remote_addr[16]; /* endpoint.addr: the source IP address, IPv4 in the first 4 bytes        */
+    uint8_t local_addr[16];  /* local_address: the destination IP address, likewise                    */
+} smol_csum_udpmeta_t;
+#define SMOL_UMETA_PACKET  1u /* PacketMetadata::packet  */
+#define SMOL_UMETA_PADDING 2u /* PacketMetadata::padding: only size and kind are set, every other byte is 0 */
+
+/* One record's outcome (16 bytes, 16-byte-aligned device array, output; one per RECORD). */
+typedef struct {
+    uint32_t ring_off; /* payload-ring index of the first byte (0 without SMOL_URX_ENQUEUED)          */
+    uint32_t len;      /* payload bytes: the size enqueue was (or would have been) called with        */
+    uint32_t meta_idx; /* metadata-ring index of its PACKET entry (0 without SMOL_URX_ENQUEUED)       */
+    uint16_t off;      /* record-relative offset of the payload (smol_csum_span_t.off)                */
+    uint8_t flags;     /* SMOL_URX_*                                                                  */
+    uint8_t reserved;  /* 0 */
+} smol_csum_udprx_t;
+#define SMOL_URX_UDP      0x01u /* a candidate: a UDP payload span under verify_copy's rule, to the socket's port */
+#define SMOL_URX_ENQUEUED 0x02u /* accepted, and enqueue returned Ok: payload and metadata entry are in place    */
+#define SMOL_URX_FULL     0x04u /* accepted, and enqueue returned Err(Full)                                      */
+#define SMOL_URX_PADDED   0x08u /* a PADDING entry was enqueued in front of it (possible together with FULL)     */
+#define SMOL_URX_RESTORED 0x10u /* stored in the second pass (see Two layouts)                                   */
+
+/* One socket's outcome (32 bytes, 16-byte-aligned device array, output; one per GROUP). */
+typedef struct {
+    uint32_t payload_read; /* the ring state after the poll: what the caller copies into its PacketBuffer */
+    uint32_t payload_len;
+    uint32_t meta_read;
+    uint32_t meta_len;
+    uint32_t enqueued;     /* records with SMOL_URX_ENQUEUED */
+    uint32_t full;         /* records with SMOL_URX_FULL     */
+    uint32_t restored;     /* records with SMOL_URX_RESTORED */
+    uint8_t valid;         /* 1: the group and its socket entry were usable */
+    uint8_t reserved[3];   /* 0 */
+} smol_csum_udpsockout_t;
+
+/* verify, and every UDP datagram's payload delivered to the place its socket's receive buffer gives it, the
+ * metadata entries written, in one pass over the frames: the UDP counterpart of
+ * smol_csum_batch_verify_tcp_assemble.  For TCP a payload's place follows from the segment's own header.  For
+ * UDP it follows from the socket's PacketBuffer (src/storage/packet_buffer.rs:80-118): from the payload ring's
+ * contiguous window, with a padding entry written when the packet would wrap; from a second ring of metadata
+ * entries, which can fill up on its own; and from the sizes of every datagram the socket accepted earlier in
+ * the same poll.  That last set depends on checksum verdicts: process_udp drops a datagram that fails
+ * UdpRepr::parse before any socket sees it (src/iface/interface/udp.rs:19-36), so a bad datagram takes no
+ * space.  In the reference UdpRepr::parse sums the datagram (src/wire/udp.rs:250-257) and UdpSocket::process
+ * (src/socket/udp.rs:492-529) then calls rx_buffer.enqueue(size, metadata) and copy_from_slice(payload): two
+ * passes over the payload.  Here, when every candidate is accepted, each frame byte is read once and its
+ * 128-byte header window once more.
+ *
+ * Groups.  smol_csum_frag_group_t is reused unchanged: a group is the frames the caller routes to one UDP
+ * socket in one poll, `count` consecutive records from `first`, in arrival order.  The caller demultiplexes by
+ * address, as it forms TCP groups (the address half of UdpSocket::accepts, src/socket/udp.rs:477-490, needs
+ * the interface's addresses); the device checks the port half.  d_socks and d_out have one entry per GROUP,
+ * d_status and d_rx one per RECORD.  A group is invalid when first >= n, count > n - first, count is 0 or above
+ * SMOL_MAX_SOCKET_DGRAMS, the group's or the socket entry's reserved words are not 0, payload_len >
+ * payload_cap, meta_len > meta_cap, or a ring's read index is not below its capacity (with capacity 0 it must
+ * be 0).  For an invalid group no record is read, no status byte, record entry or metadata entry is written,
+ * nothing is stored, and the group's entry of d_out is all zero.  Records outside every group are not written.
+ * Groups must not share records.
+ *
+ * Status.  d_status[i] is exactly the byte smol_csum_batch_verify writes for record i under caps.
+ *
+ * Candidate.  A record is a candidate (SMOL_URX_UDP) when smol_csum_batch_verify_copy would give it a span,
+ * the protocol is UDP, and the UDP destination port equals the group's `port`.  Its size is that span's len
+ * (the UDP length field less 8; Ethernet padding is excluded), off is verify_copy's off.  Every other record
+ * (TCP, ICMP, IGMP, fragments, malformed and unsupported records, SMOL_REC_IPHDR_ONLY, SMOL_KIND_RAW, non-IP
+ * ethertypes, another destination port) gets an all-zero entry and stores nothing.  A candidate is ACCEPTED
+ * when status & SMOL_ST_ACCEPT.
+ *
+ * The enqueue rule (packet_buffer.rs:80-118; ring_buffer.rs:76-105, 181-211).  State: the capacities
+ * P = payload_cap, M = meta_cap and (pr, pl, mr, ml) = (payload_read, payload_len, meta_read, meta_len).  For a
+ * datagram of `size`:
+ *   1. P < size or ml == M: Full, nothing changes.
+ *   2. pl == 0: pr = 0.
+ *   3. window = P - pl; widx = P ? (pr + pl) % P : 0; contig = min(window, P - widx).
+ *   4. window < size: Full.
+ *   5. Else contig < size: when window - contig < size: Full; otherwise a PADDING(contig) entry is written at
+ *      metadata index (mr + ml) % M, ml += 1, pl += contig.
+ *   6. ml == M: Full.  The padding stays: this is the reference's behaviour, so PADDED and FULL can be set
+ *      together.
+ *   7. The PACKET entry is written at metadata index (mr + ml) % M, ml += 1; ring_off = (pr + pl) % P, or 0
+ *      when P == 0; pl += size.
+ * A delivered payload is always one contiguous piece: bytes d_dst[dst_offset + ring_off ..][.. size].  A
+ * zero-length datagram takes a metadata entry and no payload byte.  Metadata index i of a group is
+ * d_meta[meta_first + i].
+ *
+ * Two layouts.  The ACCEPTED LAYOUT is the rule run over the group's accepted candidates in order.  It defines
+ * every record entry, the metadata entries and the state in d_out; a candidate that is not accepted has
+ * flags == SMOL_URX_UDP, its len and off, and takes no space.  The SPECULATIVE LAYOUT is the same rule run over
+ * all candidates in order: what the layout would be if nothing failed its gates.  THE COPY DOES NOT WAIT FOR
+ * THE VERDICT: a candidate the speculative layout enqueues is stored at its speculative place while it is
+ * summed.  Once every verdict of the group is known, each ENQUEUED record with len > 0 that was not stored, or
+ * whose place in the accepted layout differs from its speculative one, is stored again at its final place and
+ * gets SMOL_URX_RESTORED.  Speculative ranges are pairwise disjoint and so are accepted ranges, so a record
+ * that kept its place is never overwritten.  With every candidate accepted (a healthy link, or caps.udp not
+ * checking on receive) the layouts are equal and nothing is stored twice.
+ *
+ * Writes.
+ *   - Metadata: exactly the entries the accepted layout enqueues are written, PACKET and PADDING; no other
+ *     entry of d_meta is touched.
+ *   - Every byte of an ENQUEUED record's range holds its payload byte.
+ *   - A byte that lies in a speculative-layout range and in no accepted-layout range holds either what it held
+ *     before the call or the byte the speculative layout puts there: unallocated ring space, which the caller
+ *     never commits.
+ *   - Every other byte of d_dst is never written: occupied ring bytes, padding, the bytes between rings.
+ *   - No byte of d_dst is ever read.  Edges go out as byte-masked stores, never read-modify-write, so rings may
+ *     lie back to back at any alignment.  Rings of different groups must not overlap each other or the batch,
+ *     and neither may their metadata rings.  d_buf is only read, and only in 16-byte chunks that hold at least
+ *     one byte of a record.
+ *
+ * What stays with the caller.
+ *   - The address half of UdpSocket::accepts: a group is what the caller routed to the socket.
+ *   - DNS sockets, which match on the source port (src/socket/dns.rs), and DHCP and raw sockets.
+ *   - The Port Unreachable answer for a port no socket is bound to: smol_csum_batch_verify_unreach_reply.
+ *   - Dequeueing (PacketBuffer::dequeue skips the PADDING entries), and the socket's waker.
+ *   - The commit: copy the four state words of d_out into the PacketBuffer.
+ *
+ * Resources.  No context scratch, no event, no allocation; stream-ordered on `stream`, graph-capturable, and
+ * calls on different streams are independent (also on one context).
+ *
+ * SMOL_EINVAL: NULL ctx, bad caps, NULL d_groups / d_dst / d_socks / d_meta / d_status / d_rx / d_out with
+ * n_groups > 0, d_groups, d_socks, d_meta, d_rx or d_out not 16-byte aligned.  SMOL_ERANGE: as verify.
+ * n_groups == 0 returns SMOL_OK and launches nothing.
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive, as verify_unreach_reply was). */
+int smol_csum_batch_verify_udp_enqueue(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* batch,
+                                       const smol_csum_frag_group_t* d_groups, uint64_t n_groups,
+                                       const smol_checksum_caps_t* caps, uint8_t* d_dst,
+                                       const smol_csum_udpsock_t* d_socks, /* one per GROUP  */
+                                       smol_csum_udpmeta_t* d_meta,        /* the metadata rings */
+                                       uint8_t* d_status,                  /* one per RECORD */
+                                       smol_csum_udprx_t* d_rx,            /* one per RECORD */
+                                       smol_csum_udpsockout_t* d_out,      /* one per GROUP  */
+                                       void* stream);
 
 /* ---- 4. 6LoWPAN next-header-compressed UDP (RFC 6282 §4.3) ------------------------------- */
 

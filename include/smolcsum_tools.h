@@ -205,6 +205,8 @@ const char* smol_csum_tool_kernel_name(const smol_csum_ctx_t* ctx, int op, int h
  * 13 = tcpcut_kernel (smol_csum_batch_tcp_segment_emit: the same);
  * 14 = tcpasm_kernel (smol_csum_batch_verify_tcp_assemble: the same);
  * 15 = echo_kernel (smol_csum_batch_verify_echo_reply: variant 0, G and U its launch shape);
+ * 16 = unreach_kernel (smol_csum_batch_verify_unreach_reply: the same);
+ * 17 = udprx_kernel (smol_csum_batch_verify_udp_enqueue: variant 0, G 64, U its chunks per lane and step);
  * 0 before the first launch.  The fragment kernels of emit_frag /
  * verify_frag record nothing. */
 uint32_t smol_csum_tool_last_launch(void);

@@ -35,7 +35,7 @@ ABI_SYMBOLS = [
     "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
     "smol_csum_batch_verify_frag", "smol_csum_batch_verify_reassemble", "smol_csum_batch_fragment_emit",
     "smol_csum_batch_tcp_segment_emit", "smol_csum_batch_verify_tcp_assemble", "smol_csum_batch_verify_echo_reply",
-    "smol_csum_batch_verify_unreach_reply", "smol_csum_batch_nhc_udp_emit",
+    "smol_csum_batch_verify_unreach_reply", "smol_csum_batch_verify_udp_enqueue", "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
 ]
 TOOL_SYMBOLS = [
@@ -262,6 +262,67 @@ class UnreachC(ctypes.Structure):
     ]
 
 
+class UdpSockC(ctypes.Structure):
+    """smol_csum_udpsock_t: one UDP socket's receive buffer before the poll (smol_csum_batch_verify_udp_enqueue)."""
+
+    _fields_ = [
+        ("dst_offset", ctypes.c_uint64),
+        ("meta_first", ctypes.c_uint64),
+        ("payload_cap", ctypes.c_uint32),
+        ("payload_read", ctypes.c_uint32),
+        ("payload_len", ctypes.c_uint32),
+        ("meta_cap", ctypes.c_uint32),
+        ("meta_read", ctypes.c_uint32),
+        ("meta_len", ctypes.c_uint32),
+        ("port", ctypes.c_uint16),
+        ("reserved", ctypes.c_uint16 * 3),
+    ]
+
+
+class UdpMetaC(ctypes.Structure):
+    """smol_csum_udpmeta_t: one metadata-ring entry (smol_csum_batch_verify_udp_enqueue)."""
+
+    _fields_ = [
+        ("size", ctypes.c_uint32),
+        ("record", ctypes.c_uint32),
+        ("src_port", ctypes.c_uint16),
+        ("family", ctypes.c_uint8),
+        ("kind", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 4),
+        ("remote_addr", ctypes.c_uint8 * 16),
+        ("local_addr", ctypes.c_uint8 * 16),
+    ]
+
+
+class UdpRxC(ctypes.Structure):
+    """smol_csum_udprx_t: one record's outcome (smol_csum_batch_verify_udp_enqueue)."""
+
+    _fields_ = [
+        ("ring_off", ctypes.c_uint32),
+        ("len", ctypes.c_uint32),
+        ("meta_idx", ctypes.c_uint32),
+        ("off", ctypes.c_uint16),
+        ("flags", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8),
+    ]
+
+
+class UdpSockOutC(ctypes.Structure):
+    """smol_csum_udpsockout_t: one socket's outcome (smol_csum_batch_verify_udp_enqueue)."""
+
+    _fields_ = [
+        ("payload_read", ctypes.c_uint32),
+        ("payload_len", ctypes.c_uint32),
+        ("meta_read", ctypes.c_uint32),
+        ("meta_len", ctypes.c_uint32),
+        ("enqueued", ctypes.c_uint32),
+        ("full", ctypes.c_uint32),
+        ("restored", ctypes.c_uint32),
+        ("valid", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 3),
+    ]
+
+
 _LIBS = {}
 
 
@@ -340,6 +401,10 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.smol_csum_batch_verify_unreach_reply.argtypes = [vp, vp, ctypes.POINTER(BatchC), ctypes.POINTER(Caps),
                                                            ctypes.POINTER(EchoCfgC), vp, vp, vp, vp, vp, vp]
         L.smol_csum_batch_verify_unreach_reply.restype = i32
+    if hasattr(L, "smol_csum_batch_verify_udp_enqueue"):
+        L.smol_csum_batch_verify_udp_enqueue.argtypes = [vp, vp, ctypes.POINTER(BatchC), vp, u64, ctypes.POINTER(Caps),
+                                                         vp, vp, vp, vp, vp, vp, vp]
+        L.smol_csum_batch_verify_udp_enqueue.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []

@@ -525,6 +525,26 @@ int smol_csum_batch_verify_tcp_assemble(smol_csum_ctx_t* ctx, const uint8_t* d_b
                      [&] { return launch_tcpasm(p, d_groups, n_groups, v, ctx->max_blocks, (hipStream_t)stream); });
 }
 
+// Verify with every UDP datagram's payload delivered to the place its socket's PacketBuffer::enqueue gives it,
+// metadata entries written, in the same pass (include/smolcsum.h).  Uses none of the context's scratch or
+// events, so calls on different streams are independent.
+int smol_csum_batch_verify_udp_enqueue(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
+                                       const smol_csum_frag_group_t* d_groups, uint64_t n_groups,
+                                       const smol_checksum_caps_t* caps, uint8_t* d_dst, const smol_csum_udpsock_t* d_socks,
+                                       smol_csum_udpmeta_t* d_meta, uint8_t* d_status, smol_csum_udprx_t* d_rx,
+                                       smol_csum_udpsockout_t* d_out, void* stream) {
+    int rc;
+    if (!begin_group_call(ctx, caps, b, d_buf, d_groups, n_groups, &rc)) return rc;
+    if (!d_dst || !d_socks || !d_meta || !d_status || !d_rx || !d_out || ((uintptr_t)d_socks & 15u) != 0 ||
+        ((uintptr_t)d_meta & 15u) != 0 || ((uintptr_t)d_rx & 15u) != 0 || ((uintptr_t)d_out & 15u) != 0)
+        return SMOL_EINVAL;
+    KParams p = base_params(ctx, d_buf, b, caps);
+    p.status = d_status;
+    const UdpRxArgs v = {d_dst, d_socks, d_meta, d_rx, d_out};
+    return on_device(ctx, "verify_udp_enqueue kernel launch",
+                     [&] { return launch_udprx(p, d_groups, n_groups, v, ctx->max_blocks, (hipStream_t)stream); });
+}
+
 // ---- 6LoWPAN NHC UDP --------------------------------------------------------------------------
 
 int smol_csum_batch_nhc_udp_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,

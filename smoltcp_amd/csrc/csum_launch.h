@@ -259,11 +259,12 @@ __device__ inline uint64_t logical_block(uint32_t xcd_remap) {
 // KERN_TCPASM: smol_csum_batch_verify_tcp_assemble's kernel (the same).
 // KERN_ECHO: smol_csum_batch_verify_echo_reply's kernel (no registry row; variant 0, G and U its launch shape).
 // KERN_UNREACH: smol_csum_batch_verify_unreach_reply's kernel (the same).
+// KERN_UDPRX: smol_csum_batch_verify_udp_enqueue's kernel (no registry row; variant 0, G 64, U its chunks per lane).
 enum {
     KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6,
     KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9, KERN_VCOPY = 10,
     KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12, KERN_TCPCUT = 13, KERN_TCPASM = 14, KERN_ECHO = 15,
-    KERN_UNREACH = 16
+    KERN_UNREACH = 16, KERN_UDPRX = 17
 };
 inline std::atomic<uint32_t> g_last_launch{0};
 inline void note_launch(uint32_t kern, uint32_t var, uint32_t g, uint32_t u) {
@@ -418,6 +419,18 @@ struct UnreachArgs {
     uint32_t bcast_v4;              // smol_csum_echo_cfg_t.bcast_v4 as a big-endian word (0: none)
 };
 hipError_t launch_unreach(int shape, const KParams& p, const UnreachArgs& v, uint32_t max_blocks, hipStream_t s);
+// verify_udp_enqueue (smol_csum_batch_verify_udp_enqueue, csum_udprx.hip): verify's status bytes, and every UDP
+// datagram's payload stored where its socket's PacketBuffer::enqueue places it (csum_pktbuf.h), the metadata
+// entries written, in the same pass; one workgroup per group.  Outside the variant registry.
+struct UdpRxArgs {
+    uint8_t* dst;
+    const smol_csum_udpsock_t* socks;  // one 48-B entry per group (input)
+    smol_csum_udpmeta_t* meta;         // the metadata rings: 48-B entries (output)
+    smol_csum_udprx_t* rx;             // one 16-B entry per record (output)
+    smol_csum_udpsockout_t* out;       // one 32-B entry per group (output)
+};
+hipError_t launch_udprx(const KParams& p, const smol_csum_frag_group_t* groups, uint64_t ngroups,
+                        const UdpRxArgs& v, uint32_t max_blocks, hipStream_t s);
 hipError_t launch_stream_read(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t max_blocks,
                               hipStream_t s);
 hipError_t launch_field_probe(uint8_t* buf, uint64_t bytes, uint64_t stride, uint32_t f1, uint32_t f2,

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import (NO_FIELD, BatchC, Caps, DgramC, EchoC, EchoCfgC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, TcpFlowC,
-                   TcpOutC, TcpPlanC, TcpSegC, TcpWinC, UnreachC, check, lib)
+                   TcpOutC, TcpPlanC, TcpSegC, TcpWinC, UdpMetaC, UdpRxC, UdpSockC, UdpSockOutC, UnreachC, check, lib)
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -97,6 +97,25 @@ ECHO_REQUEST, ECHO_ANSWERED, ECHO_WRITTEN, ECHO_SEND, ECHO_HOST = 0x01, 0x02, 0x
 UNR_DTYPE = np.dtype([("frame_len", "<u4"), ("data_off", "<u2"), ("head_len", "u1"), ("flags", "u1")])
 assert UNR_DTYPE.itemsize == 8 == ctypes.sizeof(UnreachC)
 UNR_REFUSED, UNR_ANSWERED, UNR_WRITTEN, UNR_SEND, UNR_HOST, UNR_PORT = 0x01, 0x02, 0x04, 0x08, 0x10, 0x20  # SMOL_UNR_*
+# smol_csum_udpsock_t / smol_csum_udpmeta_t / smol_csum_udprx_t / smol_csum_udpsockout_t: a UDP socket's receive
+# buffer before the poll, a metadata-ring entry, a record's and a socket's outcome (smol_csum_batch_verify_udp_enqueue)
+UDPSOCK_DTYPE = np.dtype([("dst_offset", "<u8"), ("meta_first", "<u8"), ("payload_cap", "<u4"), ("payload_read", "<u4"),
+                          ("payload_len", "<u4"), ("meta_cap", "<u4"), ("meta_read", "<u4"), ("meta_len", "<u4"),
+                          ("port", "<u2"), ("reserved", "<u2", (3,))])
+assert UDPSOCK_DTYPE.itemsize == 48 == ctypes.sizeof(UdpSockC)
+UDPMETA_DTYPE = np.dtype([("size", "<u4"), ("record", "<u4"), ("src_port", "<u2"), ("family", "u1"), ("kind", "u1"),
+                          ("reserved", "u1", (4,)), ("remote_addr", "u1", (16,)), ("local_addr", "u1", (16,))])
+assert UDPMETA_DTYPE.itemsize == 48 == ctypes.sizeof(UdpMetaC)
+UDPRX_DTYPE = np.dtype([("ring_off", "<u4"), ("len", "<u4"), ("meta_idx", "<u4"), ("off", "<u2"), ("flags", "u1"),
+                        ("reserved", "u1")])
+assert UDPRX_DTYPE.itemsize == 16 == ctypes.sizeof(UdpRxC)
+UDPSOCKOUT_DTYPE = np.dtype([("payload_read", "<u4"), ("payload_len", "<u4"), ("meta_read", "<u4"), ("meta_len", "<u4"),
+                             ("enqueued", "<u4"), ("full", "<u4"), ("restored", "<u4"), ("valid", "u1"),
+                             ("reserved", "u1", (3,))])
+assert UDPSOCKOUT_DTYPE.itemsize == 32 == ctypes.sizeof(UdpSockOutC)
+MAX_SOCKET_DGRAMS = 256
+URX_UDP, URX_ENQUEUED, URX_FULL, URX_PADDED, URX_RESTORED = 0x01, 0x02, 0x04, 0x08, 0x10  # SMOL_URX_*
+UMETA_PACKET, UMETA_PADDING = 1, 2  # SMOL_UMETA_*
 
 
 def make_port_map(open_ports) -> np.ndarray:
@@ -153,6 +172,22 @@ def make_tcpwins(dst_offsets, ring_lens, ring_poss, window_starts, window_lens) 
     w["window_start"] = np.broadcast_to(np.asarray(window_starts, dtype=np.uint32), (n,))
     w["window_len"] = np.broadcast_to(np.asarray(window_lens, dtype=np.uint32), (n,))
     return w
+
+
+def make_udpsocks(dst_offsets, meta_firsts, payload_caps, payload_reads, payload_lens, meta_caps, meta_reads, meta_lens,
+                  ports) -> np.ndarray:
+    """Host array of smol_csum_udpsock_t (view it as uint8 and copy it to the device): per socket, where its
+    payload ring's storage lies in `dst`, where its metadata ring's first entry lies in `meta`, the two rings'
+    capacity / read index / length as the PacketBuffer holds them before the poll, and the bound port."""
+    n = len(dst_offsets)
+    s = np.zeros(n, dtype=UDPSOCK_DTYPE)
+    s["dst_offset"] = np.asarray(dst_offsets, dtype=np.uint64)
+    s["meta_first"] = np.broadcast_to(np.asarray(meta_firsts, dtype=np.uint64), (n,))
+    for name, val in (("payload_cap", payload_caps), ("payload_read", payload_reads), ("payload_len", payload_lens),
+                      ("meta_cap", meta_caps), ("meta_read", meta_reads), ("meta_len", meta_lens)):
+        s[name] = np.broadcast_to(np.asarray(val, dtype=np.uint32), (n,))
+    s["port"] = np.broadcast_to(np.asarray(ports, dtype=np.uint16), (n,))
+    return s
 
 
 def apply_fields(host_buf: np.ndarray, record_offsets, record_lens, fields) -> np.ndarray:
@@ -638,6 +673,44 @@ class ChecksumEngine:
               "smol_csum_batch_verify_unreach_reply")
         return status, unr
 
+    def verify_udp_enqueue(self, buf, batch: Batch, groups, dst, socks, meta, caps=None, status=None, rx=None, out=None,
+                           stream=None):
+        """verify, and in the same pass every UDP datagram's payload put where its socket's
+        PacketBuffer::enqueue places it in `dst`, the metadata entries written to `meta`
+        (smol_csum_batch_verify_udp_enqueue).  `groups`: a device uint8 tensor of smol_csum_frag_group_t (see
+        make_groups), one per socket: the frames routed to it in this poll, consecutive records in arrival
+        order; `socks`: a device uint8 tensor of one smol_csum_udpsock_t per GROUP (see make_udpsocks); `dst`:
+        the uint8 device tensor that holds the payload rings; `meta`: the 16-byte aligned uint8 device tensor
+        that holds the metadata rings (48 bytes per entry, UDPMETA_DTYPE).  Returns (status, rx, out): verify's
+        status byte per record (a fresh tensor starts zeroed; records outside the groups keep their value), an
+        n x 16 uint8 device tensor of smol_csum_udprx_t (UDPRX_DTYPE; a fresh one starts zeroed) and an
+        n_groups x 32 one of smol_csum_udpsockout_t (UDPSOCKOUT_DTYPE).  The copy does not wait for the
+        verdict: commit by copying the four state words of `out` into the socket's PacketBuffer."""
+        import torch
+
+        self._check_buf(buf, batch)
+        assert groups.is_cuda and groups.numel() % 16 == 0
+        ng = groups.numel() // 16
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert socks.is_cuda and socks.is_contiguous() and socks.numel() * socks.dtype.itemsize >= 48 * ng
+        assert meta.is_cuda and meta.is_contiguous()
+        if status is None:
+            status = torch.zeros(batch.n, dtype=torch.uint8, device=buf.device)
+        if rx is None:
+            rx = torch.zeros((batch.n, 16), dtype=torch.uint8, device=buf.device)
+        if out is None:
+            out = torch.empty((ng, 32), dtype=torch.uint8, device=buf.device)
+        assert rx.is_cuda and rx.is_contiguous() and rx.numel() * rx.dtype.itemsize >= 16 * batch.n
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.dtype.itemsize >= 32 * ng
+        b = batch.c()
+        c = _caps(caps)
+        check(self._L.smol_csum_batch_verify_udp_enqueue(self._h, buf.data_ptr(), ctypes.byref(b), groups.data_ptr(), ng,
+                                                       ctypes.byref(c), dst.data_ptr(), socks.data_ptr(), meta.data_ptr(),
+                                                       status.data_ptr(), rx.data_ptr(), out.data_ptr(),
+                                                       self._stream(stream)),
+              "smol_csum_batch_verify_udp_enqueue")
+        return status, rx, out
+
     # ---- tooling ----
     def synth(self, buf, batch: Batch, profile: int, seed: int, stream=None):
         self._check_buf(buf, batch)
@@ -748,13 +821,14 @@ class ChecksumEngine:
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
         "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
-        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel" | verify_tcp_assemble's "tcpasm_kernel" | verify_echo_reply's "echo" | verify_unreach_reply's "unreach", "variant": VAR, "G":
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel" | verify_tcp_assemble's "tcpasm_kernel" | verify_echo_reply's "echo" | verify_unreach_reply's "unreach" | verify_udp_enqueue's "udprx_kernel", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
                  6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel",
-                 11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel", 14: "tcpasm_kernel", 15: "echo", 16: "unreach"}
+                 11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel", 14: "tcpasm_kernel", 15: "echo", 16: "unreach",
+                 17: "udprx_kernel"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

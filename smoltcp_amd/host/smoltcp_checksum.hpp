@@ -348,6 +348,25 @@ public:
               "smol_csum_batch_verify_unreach_reply");
     }
 
+    // verify, and in the same pass every UDP datagram's payload stored where its socket's PacketBuffer::enqueue
+    // places it (src/storage/packet_buffer.rs:80-118), the metadata entries written: UdpSocket::process'
+    // rx_buffer.enqueue and copy_from_slice (src/socket/udp.rs:492-529) behind UdpRepr::parse's sum.  A group is
+    // the frames the caller routed to one socket in this poll, in arrival order; d_socks[g] is that socket's ring
+    // state before the poll and its port, d_out[g] the state after it.  d_status and d_rx are per record, d_meta
+    // holds the metadata rings.  The copy waits for no verdict: commit by copying d_out[g]'s four state words
+    // into the PacketBuffer.  d_buf is only read.
+    void verify_udp_enqueue(const uint8_t* d_buf, const Batch& b, const smol_csum_frag_group_t* d_groups,
+                            uint64_t n_groups, uint8_t* d_dst, const smol_csum_udpsock_t* d_socks,
+                            smol_csum_udpmeta_t* d_meta, uint8_t* d_status, smol_csum_udprx_t* d_rx,
+                            smol_csum_udpsockout_t* d_out, const smoltcp::phy::ChecksumCapabilities& caps = {},
+                            void* stream = nullptr) {
+        auto bc = b.c();
+        auto cc = caps.c();
+        check(smol_csum_batch_verify_udp_enqueue(ctx_, d_buf, &bc, d_groups, n_groups, &cc, d_dst, d_socks, d_meta, d_status,
+                                                 d_rx, d_out, stream),
+              "smol_csum_batch_verify_udp_enqueue");
+    }
+
     // 6LoWPAN NHC UDP (sixlowpan::nhc::UdpNhcRepr::emit / ::parse): every record is a LOWPAN_NHC
     // UDP packet; d_addrs[i] holds record i's IPv6 addresses (IPHC-decompressed).
     void nhc_udp_emit(uint8_t* d_buf, const Batch& b, const smol_ipv6_addr_pair_t* d_addrs,
