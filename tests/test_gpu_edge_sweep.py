@@ -67,10 +67,10 @@ def expected_launch(variant: int, op: str, fixed: bool, field_stores: bool = Fal
 
 
 class Case:
-    """One placed batch: its bytes as verify sees them, emit's input (0xA5A5 in every checksum field), the
-    device copies (uploaded once) and the oracle's results per caps (computed once)."""
+    """One placed batch: its bytes as verify sees them, emit's input (`fill` in both bytes of every checksum
+    field: 0xA5A5), the device copies (uploaded once) and the oracle's results per caps (computed once)."""
 
-    def __init__(self, pl: S.Placed):
+    def __init__(self, pl: S.Placed, fill: int = 0xA5):
         self.pl, self.n, self.fixed = pl, pl.n, pl.stride != 0
         self.kind, self.rflags = (int(pl.kinds[0]), int(pl.flags[0])) if self.fixed else (0, 0)  # (per record otherwise)
         self.host = pl.buf
@@ -80,7 +80,7 @@ class Case:
         for o, r, k, f in zip(self.offs, self.recs, pl.kinds, pl.flags):
             for fo in S.field_offsets(r, int(k), int(f)):
                 if fo is not None:
-                    self.raw[o + fo:o + fo + 2] = 0xA5
+                    self.raw[o + fo:o + fo + 2] = fill
         self.desc = None if self.fixed else E.make_descriptors(pl.offs, pl.lens, pl.kinds, pl.flags)
         self._dev, self._ref = {}, {}
 
@@ -115,24 +115,32 @@ class Case:
 
 
 class Sweep:
-    def __init__(self):
-        self.corpus = S.build_corpus()
+    """The placed corpus per layout.  `corpus`: another one than the edge sweep's, `case`: what wraps a placement
+    (tests/test_gpu_sum_sweep.py).  Records longer than S.LMAX, of which the edge sweep's corpus has none, are for
+    the two descriptor layouts only: place_fixed would cut them.  `limit`: the largest fixed-stride buffer; above
+    it place_fixed gives up records that meet no new edge cell."""
+
+    def __init__(self, corpus=None, case=Case, limit=64 << 20):
+        self.corpus = S.build_corpus() if corpus is None else corpus
+        self.case, self.limit = case, limit
+        self.short = [r for r in self.corpus if len(r.data) <= S.LMAX]
         # what verify_tcp_assemble is given: see test_verify_tcp_assemble
-        self.tcp_corpus = [r for r in self.corpus if S.geometry(r.data, r.kind, emit=True).proto == S.P_TCP]
+        self.tcp_corpus = [r for r in self.short if S.geometry(r.data, r.kind, emit=True).proto == S.P_TCP]
         self._forms = {}
 
     def cases(self, form):
         if form not in self._forms:
-            c, both = self.corpus, [(k, f) for k in (S.KIND_IP, S.KIND_ETH) for f in (0, S.REC_IPHDR_ONLY)]
+            c = self.short
+            both = [(k, f) for k in (S.KIND_IP, S.KIND_ETH) for f in (0, S.REC_IPHDR_ONLY) if any(r.flags == f for r in c)]
             v4 = [r for r in c if r.family.startswith("v4/")]
             if form in DESC_FORMS:
-                pls = [S.place_desc(c, gaps=form == "gaps")]
+                pls = [S.place_desc(self.corpus, gaps=form == "gaps")]
             elif form == "fixed":
                 pls = [S.place_fixed(c, k, f) for k, f in both]
             elif form == "fixed2304":
-                pls = [S.place_fixed(c, k, f, 2304, 2305) for k, f in both]
+                pls = [S.place_fixed(c, k, f, 2304, 2305, limit=self.limit) for k, f in both]
             elif form == "fixed4032":
-                pls = [S.place_fixed(c, k, 0, 4032, 4033) for k in (S.KIND_IP, S.KIND_ETH)]
+                pls = [S.place_fixed(c, k, 0, 4032, 4033, limit=self.limit) for k in (S.KIND_IP, S.KIND_ETH)]
             elif form == "route":  # see test_emit_route
                 pls = [S.place_fixed(c, k, 0, S.LMAX + 1, S.LMAX + 1) for k in (S.KIND_IP, S.KIND_ETH)]
             elif form == "v4gaps":
@@ -144,7 +152,7 @@ class Sweep:
                 pls = [S.place_desc(self.tcp_corpus, gaps=True)]
             elif form == "tcpfixed":
                 pls = [S.place_fixed(self.tcp_corpus, k, 0) for k in (S.KIND_IP, S.KIND_ETH)]
-            self._forms[form] = [Case(pl) for pl in pls]
+            self._forms[form] = [self.case(pl) for pl in pls]
         return self._forms[form]
 
 
