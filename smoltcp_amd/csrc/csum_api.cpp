@@ -376,6 +376,17 @@ int smol_csum_batch_verify_copy(smol_csum_ctx_t* ctx, const uint8_t* d_buf, cons
     });
 }
 
+// The responders' configuration (NULL: none): false when a reserved byte is set; *bcast is the interface's
+// IPv4 broadcast address as a big-endian word, 0 without one.
+static bool responder_cfg(const smol_csum_echo_cfg_t* cfg, uint32_t* bcast) {
+    *bcast = 0;
+    if (!cfg) return true;
+    if (cfg->reserved[0] | cfg->reserved[1] | cfg->reserved[2] | cfg->reserved[3]) return false;
+    *bcast = (uint32_t)cfg->bcast_v4[0] << 24 | (uint32_t)cfg->bcast_v4[1] << 16 | (uint32_t)cfg->bcast_v4[2] << 8 |
+             (uint32_t)cfg->bcast_v4[3];
+    return true;
+}
+
 // Verify with the replies to the batch's echo requests written in the same pass (include/smolcsum.h).  Uses
 // none of the context's scratch or events, so calls on different streams are independent.
 int smol_csum_batch_verify_echo_reply(smol_csum_ctx_t* ctx, const uint8_t* d_buf, const smol_csum_batch_t* b,
@@ -385,15 +396,13 @@ int smol_csum_batch_verify_echo_reply(smol_csum_ctx_t* ctx, const uint8_t* d_buf
     int rc;
     const bool work = begin_call(ctx, caps, b, d_buf, &rc);
     if (rc != SMOL_OK) return rc;
-    if (cfg && (cfg->reserved[0] | cfg->reserved[1] | cfg->reserved[2] | cfg->reserved[3])) return SMOL_EINVAL;
+    uint32_t bcast;
+    if (!responder_cfg(cfg, &bcast)) return SMOL_EINVAL;
     if (!work) return rc;
     if (!d_dst || !d_slots || !d_status || !d_echo || ((uintptr_t)d_slots & 15u) != 0 || ((uintptr_t)d_echo & 7u) != 0)
         return SMOL_EINVAL;
     KParams p = base_params(ctx, d_buf, b, caps);
     p.status = d_status;
-    const uint32_t bcast = cfg ? (uint32_t)cfg->bcast_v4[0] << 24 | (uint32_t)cfg->bcast_v4[1] << 16 |
-                                     (uint32_t)cfg->bcast_v4[2] << 8 | (uint32_t)cfg->bcast_v4[3]
-                               : 0u;
     const hipStream_t s = (hipStream_t)stream;
     const int shape = ctx->shape >= 0 ? ctx->shape : echo_shape(b->len, b->desc != nullptr);
     return on_device(ctx, "verify_echo_reply kernel launch", [&] {
@@ -413,15 +422,13 @@ int smol_csum_batch_verify_unreach_reply(smol_csum_ctx_t* ctx, const uint8_t* d_
     int rc;
     const bool work = begin_call(ctx, caps, b, d_buf, &rc);
     if (rc != SMOL_OK) return rc;
-    if (cfg && (cfg->reserved[0] | cfg->reserved[1] | cfg->reserved[2] | cfg->reserved[3])) return SMOL_EINVAL;
+    uint32_t bcast;
+    if (!responder_cfg(cfg, &bcast)) return SMOL_EINVAL;
     if (!work) return rc;
     if (!d_dst || !d_slots || !d_status || !d_unr || ((uintptr_t)d_slots & 15u) != 0 || ((uintptr_t)d_unr & 7u) != 0)
         return SMOL_EINVAL;
     KParams p = base_params(ctx, d_buf, b, caps);
     p.status = d_status;
-    const uint32_t bcast = cfg ? (uint32_t)cfg->bcast_v4[0] << 24 | (uint32_t)cfg->bcast_v4[1] << 16 |
-                                     (uint32_t)cfg->bcast_v4[2] << 8 | (uint32_t)cfg->bcast_v4[3]
-                               : 0u;
     const hipStream_t s = (hipStream_t)stream;
     const int shape = ctx->shape >= 0 ? ctx->shape : unreach_shape(b->len, b->desc != nullptr);
     return on_device(ctx, "verify_unreach_reply kernel launch", [&] {

@@ -10,12 +10,13 @@
 //
 // One 256-thread workgroup per group (fragcopy_kernel's shape, csum_fraggroup.h's group_valid, lds_sync and
 // wave reductions), grid-stride over groups.
-//   1. Record j goes to wave j mod 4.  The wave streams it as vcopy_kernel<64, U> does: step 0's 128-B header
-//      window goes to the wave's LDS window, parse_geometry<false> parses it, every chunk is loaded once and
-//      summed once, finish_gates (MODE_VERIFY) writes the status byte and leaves it in LDS.  The store part
-//      differs in two ways: the delivered range is the payload trimmed to the window (csum_tcpwin.h), and the
-//      destination is one or two pieces of the ring, so a wrapped record runs the store part twice over the
-//      same registers, each piece with its own funnel shift.  The copy waits for no verdict.
+//   1. Record j goes to wave j mod 4.  The wave streams it with csum_deliver.h's pieces for G = 64 (load_step,
+//      Record::parse, sum_step, store_step, finish): step 0's 128-B header window goes to the wave's LDS
+//      window, parse_geometry<false> parses it, every chunk is loaded once and summed once, finish_gates
+//      (MODE_VERIFY) writes the status byte and leaves it in LDS.  This file's own: the delivered range is the
+//      payload trimmed to the window (csum_tcpwin.h), and the destination is one or two pieces of the ring, so
+//      a record is stored into two Dests from the same registers, each piece with its own funnel shift (the
+//      second is empty unless the range wraps).  The copy waits for no verdict.
 //   2. Barrier (all threads, whatever the group streamed).  Thread j holds record j's window range and class
 //      (delivered, counted) from LDS and scans the group's ranges once: a counted record that meets a
 //      delivered, not counted one is redelivered; contig_len is the smallest of 0 and the counted ends that
@@ -24,18 +25,17 @@
 //   3. When anything is redelivered: an agent-scope release fence in front of a barrier completes the first
 //      pass's stores, then the waves stream those records again, copy only.
 //   4. Thread j writes record j's segment entry, thread 0 the flow entry.
-// What is duplicated: the streaming body of step 1 is vcopy_kernel's loop for G = 64 written out again.
-// vcopy_kernel stores one piece per record with a compile-time group size; sharing the body would change its
-// code, so it is left alone.
 //
 // Every barrier is reached by all 256 threads: an invalid group is skipped by the whole workgroup before the
 // first one, and the redelivery barrier is taken on a value every thread reads from LDS.
+#include "csum_deliver.h"
 #include "csum_fraggroup.h"
 #include "csum_tcpwin.h"
 
 namespace smolcsum {
 namespace tcpasm {
 
+using namespace deliver;
 using namespace fraggroup;
 
 // Chunks per lane and step.  The kernel is bound by the latency of a record's chain (load, parse, rule, sum,
@@ -44,11 +44,8 @@ using namespace fraggroup;
 // 1.6 times as long.  A 1514-B frame is two steps.
 constexpr int U = 1;
 constexpr uint32_t STEP = 64 * U;
-constexpr int WIN = 128;  // the header window: 16-B grid
-constexpr int WIN_CH = WIN / 16;
 constexpr uint32_t MAXS = SMOL_MAX_FLOW_SEGMENTS;
 static_assert(MAXS <= 256, "thread j holds record j");
-static_assert(64 * U >= WIN_CH, "step 0 holds the window");
 static_assert(sizeof(smol_csum_tcpwin_t) == 32 && sizeof(smol_csum_tcpseg_t) == 16 && sizeof(smol_csum_tcpflow_t) == 16,
               "entry layouts");
 
@@ -61,22 +58,6 @@ __device__ __forceinline__ uint32_t wave_min(uint32_t v) {
     return v;
 }
 
-// One contiguous piece of a record's delivered range: n bytes from record offset rec_off to address D.
-// Destination chunk of record chunk k: piece-relative position 16 k + dk0 (vcopy_kernel's).
-struct Dest {
-    uint64_t D;
-    uint32_t n, sh;
-    int dk0;
-};
-__device__ __forceinline__ Dest dest_of(uint64_t a0, uint32_t head, uint32_t rec_off, uint64_t D, uint32_t n) {
-    Dest d;
-    d.D = D;
-    d.n = n;
-    d.sh = (uint32_t)((a0 + rec_off - D) & 15u);
-    d.dk0 = (int)d.sh - (int)head - (int)rec_off;
-    return d;
-}
-
 // The ring pieces of a record's delivered range, which starts at record offset src.
 struct Pieces {
     Dest a, b;
@@ -86,48 +67,6 @@ __device__ __forceinline__ Pieces pieces_of(const TcpWinRule& w, uint64_t ring, 
     q.a = dest_of(a0, head, src, ring + w.pos0, w.len0);
     q.b = dest_of(a0, head, src + w.len0, ring, w.len1);
     return q;
-}
-
-// One step's loads (vcopy_kernel's): chunks [i0, i0 + 64 U), and for lane 63 the chunk after them.
-__device__ __forceinline__ void load_step(uint64_t base, uint32_t nch, uint32_t i0, bool next, int lane, uint64_t dummy,
-                                          u32x4 (&c)[U], u32x4& xh) {
-    const uint32_t kx = i0 + STEP;
-    xh = ld16<false>((gcv4)(next && lane == 63 && kx < nch ? base + 16ull * kx : dummy));
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint32_t k = i0 + (uint32_t)(u * 64 + lane);
-        c[u] = ld16<false>((gcv4)(k < nch ? base + 16ull * k : dummy));
-    }
-}
-
-// Each chunk's successor (the wave's lanes together: the exchange needs all of them).
-__device__ __forceinline__ void successors(const u32x4 (&c)[U], const u32x4& xh, int lane, u32x4 (&hi)[U]) {
-    u32x4 ncur = vcopy::next4<64>(c[0], lane);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const u32x4 nnext = u + 1 < U ? vcopy::next4<64>(c[u + 1 < U ? u + 1 : u], lane) : xh;
-        hi[u] = lane == 63 ? nnext : ncur;
-        ncur = nnext;
-    }
-}
-
-// One step's stores into one piece: chunks entirely inside it as one dwordx4 store, its first and last
-// chunk byte-masked (store_edge).
-__device__ __forceinline__ void store_piece(const Dest& d, const u32x4 (&c)[U], const u32x4 (&hi)[U], uint32_t i0, uint32_t nch,
-                                            int lane) {
-    if (d.n == 0) return;
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint32_t k = i0 + (uint32_t)(u * 64 + lane);
-        const int pos = (int)(16u * k) + d.dk0;
-        const int lo = -pos, end = (int)d.n - pos;
-        if (k < nch && end > 0 && lo < 16) {
-            const u32x4 m = funnel16(c[u], hi[u], d.sh);
-            const gu8 dst = (gu8)(d.D + (uint64_t)(int64_t)pos);
-            if (lo <= 0 && end >= 16) *(GMEM u32x4*)dst = m;
-            else vcopy::store_edge(dst, m, lo, end);
-        }
-    }
 }
 
 template <bool IMPLICIT>
@@ -144,8 +83,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void t
     const int lane = (int)(tid & 63u);
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const uint64_t dummy = (uint64_t)p.dummy;
-    u32x4* wn = &win[wave][0];
-    const uint8_t* winb = reinterpret_cast<const uint8_t*>(wn);
 
     for (uint64_t gi = blockIdx.x; gi < ngroups; gi += gridDim.x) {
         const uint64_t first = groups[gi].first;
@@ -167,66 +104,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void t
         // DESIGN.md §6.)
         for (uint32_t j = wave; j < count; j += 4) {
             const uint64_t r = first + j;
-            const RecRef rr = rec_at<IMPLICIT, false>(p, r);
-            const uint64_t base = rr.a0 & ~15ull;
-            const uint32_t head = (uint32_t)(rr.a0 - base);
-            const uint32_t nch = n_chunks<false>(rr);
+            const Record rec(rec_at<IMPLICIT, false>(p, r), &win[wave][0], geo[wave]);
+            const uint32_t nch = rec.nch;
 
             u32x4 c[U], xh;
-            load_step(base, nch, 0u, true, lane, dummy, c, xh);
-#pragma unroll
-            for (int u = 0; u * 64 < WIN_CH; ++u) {
-                const uint32_t k = (uint32_t)(u * 64 + lane);
-                if (k < (uint32_t)WIN_CH && k < nch) wn[k] = c[u];
-            }
-            wave_lds_sync();
-            // record byte o: the LDS window, else global memory (behind a long Hop-by-Hop header)
-            auto rd = [&](uint32_t o) -> uint32_t {
-                const uint32_t x = head + o;
-                if (x < (uint32_t)WIN) return (uint32_t)winb[x];
-                return ld_byte_sync(rr.a0 + o);
-            };
-            {
-                const Geom g0 = parse_geometry<false>(rd, rr.len, rr.kind, false);
-                if (lane == 0) geo[wave] = g0;
-            }
-            wave_lds_sync();
-            const Geom& g = geo[wave];
-            const bool l4 = g.proto != P_NONE && !(g.st & SMOL_ST_MALFORMED);
-            const int s1 = l4 ? (int)g.span_end : 0;
+            load_step<64, U>(rec.base, nch, 0u, true, lane, dummy, c, xh);
+            const int s1 = rec.parse<64, U>(c, lane);
+            const Geom& g = rec.g;
 
             // the TCP payload span (verify_copy's rule), the window rule and the ring pieces
             uint32_t off = 0, seq = 0, fl = 0;
             TcpWinRule w = {0u, 0u, 0u, 0u, 0u, 0u, 0u};
             if (!(g.st & (SMOL_ST_MALFORMED | SMOL_ST_UNSUPPORTED)) && g.proto == P_TCP) {
-                const uint32_t thl = (rd(g.l4_off + 12) >> 4) * 4;
+                const uint32_t thl = (rec.rd(g.l4_off + 12) >> 4) * 4;
                 off = g.l4_off + thl;
-                seq = rd(g.l4_off + 4) << 24 | rd(g.l4_off + 5) << 16 | rd(g.l4_off + 6) << 8 | rd(g.l4_off + 7);
-                const bool syn_rst = (rd(g.l4_off + 13) & 0x06u) != 0;
+                seq = rec.rd(g.l4_off + 4) << 24 | rec.rd(g.l4_off + 5) << 16 | rec.rd(g.l4_off + 6) << 8 | rec.rd(g.l4_off + 7);
+                const bool syn_rst = (rec.rd(g.l4_off + 13) & 0x06u) != 0;
                 w = tcpwin_rule(seq, g.l4_len - thl, wstart, wlen, ring_pos, ring_len);
                 fl = SMOL_SEG_TCP | (w.in_window ? SMOL_SEG_IN_WINDOW : 0u) | (w.in_window && !syn_rst ? SMOL_SEG_COPIED : 0u);
             }
             const bool st = (fl & SMOL_SEG_COPIED) && w.len > 0;  // (wave-uniform)
-            const Pieces q = pieces_of(w, ring, rr.a0, head, off + w.trim);
+            const Pieces q = pieces_of(w, ring, rec.rr.a0, rec.head, off + w.trim);
 
             uint32_t acc = 0;
             for (uint32_t i0 = 0; i0 < nch; i0 += STEP) {
-                if (i0) load_step(base, nch, i0, st, lane, dummy, c, xh);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const uint32_t k = i0 + (uint32_t)(u * 64 + lane);
-                    if (k < nch) acc = sum_chunk(c[u], (int)(16u * k) - (int)head, s1, acc);
-                }
-                if (st) {
-                    u32x4 hi[U];
-                    successors(c, xh, lane, hi);
-                    store_piece(q.a, c, hi, i0, nch, lane);
-                    store_piece(q.b, c, hi, i0, nch, lane);
-                }
+                if (i0) load_step<64, U>(rec.base, nch, i0, st, lane, dummy, c, xh);
+                acc = sum_step<64, U>(c, i0, rec, s1, lane, acc);
+                if (st) store_step<64, U>(c, xh, i0, nch, lane, q.a, q.b);
             }
 
-            finish_gates<64, MODE_VERIFY, false, decltype(rd)>(p, g, acc, rd, winb, head, rr.a0, r, lane, nullptr, ~0ull, ~0ull,
-                                                               0, nullptr, &s_stat[j]);
+            finish<64>(p, rec, acc, r, lane, &s_stat[j]);
             if (lane == 0) {
                 s_seq[j] = seq;
                 s_woff[j] = w.win_off;
@@ -285,19 +192,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void t
             __syncthreads();                                    // ... in every wave, before the second ones issue
             for (uint32_t j = wave; j < count; j += 4) {
                 if (!((s_info[j] >> 16) & SMOL_SEG_REDELIVERED)) continue;
-                const RecRef rr = rec_at<IMPLICIT, false>(p, first + j);
-                const uint64_t base = rr.a0 & ~15ull;
-                const uint32_t head = (uint32_t)(rr.a0 - base);
-                const uint32_t nch = n_chunks<false>(rr);
+                const Record rec(rec_at<IMPLICIT, false>(p, first + j), &win[wave][0], geo[wave]);  // (its grid only)
                 TcpWinRule w = {1u, s_woff[j], s_len[j], 0u, 0u, 0u, 0u};
                 tcpwin_split(w, ring_pos, ring_len);
-                const Pieces q = pieces_of(w, ring, rr.a0, head, s_src[j]);
-                for (uint32_t i0 = 0; i0 < nch; i0 += STEP) {
-                    u32x4 c[U], xh, hi[U];
-                    load_step(base, nch, i0, true, lane, dummy, c, xh);
-                    successors(c, xh, lane, hi);
-                    store_piece(q.a, c, hi, i0, nch, lane);
-                    store_piece(q.b, c, hi, i0, nch, lane);
+                const Pieces q = pieces_of(w, ring, rec.rr.a0, rec.head, s_src[j]);
+                for (uint32_t i0 = 0; i0 < rec.nch; i0 += STEP) {
+                    u32x4 c[U], xh;
+                    load_step<64, U>(rec.base, rec.nch, i0, true, lane, dummy, c, xh);
+                    store_step<64, U>(c, xh, i0, rec.nch, lane, q.a, q.b);
                 }
             }
         }

@@ -14,9 +14,10 @@
 //      addresses and source port go to LDS.  After a barrier thread 0 runs the enqueue rule (csum_pktbuf.h)
 //      over ALL candidates in order: the speculative layout, every record's speculative ring_off in LDS.  At
 //      most 256 serial iterations, all in LDS.
-//   1. The wave streams each of its records once, as tcpasm_kernel step 1 does: every 16-B chunk is loaded
-//      once and summed as verify sums it; for a candidate the speculative layout enqueues the same registers
-//      are stored to its speculative place.  The copy waits for no verdict.  finish_gates (MODE_VERIFY) writes
+//   1. The wave streams each of its records once, with csum_deliver.h's pieces for G = 64 (load_step,
+//      Record::parse, sum_step, store_step, finish): every 16-B chunk is loaded once and summed as verify sums
+//      it; for a candidate the speculative layout enqueues the same registers are stored to its speculative
+//      place, one Dest.  The copy waits for no verdict.  finish_gates (MODE_VERIFY) writes
 //      the status byte and leaves it in LDS.
 //   2. Barrier.  Thread 0 runs the rule again over the ACCEPTED candidates: the accepted layout, every record's
 //      final place, flags and meta_idx, the PADDING entries and the group entry.  An ENQUEUED record with
@@ -35,91 +36,29 @@
 // lie in a speculative range and in no accepted range may keep a speculative byte: they are free ring space.
 // Occupied bytes and padding are in no range of either layout.
 //
-// What is duplicated: the streaming body of step 1 (load_step, successors, store_piece) is tcpasm_kernel's,
-// which is vcopy_kernel's loop for G = 64 written out.  Sharing it would change those kernels' code, so they
-// are left alone.
-//
 // Every barrier is reached by all 256 threads: an invalid group is skipped by the whole workgroup before the
 // first one, and the restore barrier is taken on a value every thread reads from LDS.
+#include "csum_deliver.h"
 #include "csum_fraggroup.h"
 #include "csum_pktbuf.h"
 
 namespace smolcsum {
 namespace udprx {
 
+using namespace deliver;
 using namespace fraggroup;
 
 // Chunks per lane and step: tcpasm_kernel's U = 1 (the kernel is bound by the latency of a record's chain,
 // so resident waves count for more than a frame in one step).  A 1514-B frame is two steps.
 constexpr int U = 1;
 constexpr uint32_t STEP = 64 * U;
-constexpr int WIN = 128;  // the header window: 16-B grid
-constexpr int WIN_CH = WIN / 16;
 constexpr uint32_t MAXD = SMOL_MAX_SOCKET_DGRAMS;
 constexpr uint32_t PRE = 8;  // records a wave parses at a time in the header pre-pass: 8 lanes each
 constexpr uint32_t NONE = ~0u;  // s_size: no candidate; s_spec: the speculative layout does not enqueue it
 static_assert(MAXD <= 256 && MAXD == MAXF, "thread j holds record j; group_valid's bound");
-static_assert(64 * U >= WIN_CH, "step 0 holds the window");
 static_assert(sizeof(smol_csum_udpsock_t) == 48 && sizeof(smol_csum_udpmeta_t) == 48 && sizeof(smol_csum_udprx_t) == 16 &&
                   sizeof(smol_csum_udpsockout_t) == 32,
               "entry layouts");
-
-// n bytes from record offset rec_off to address D.  Destination chunk of record chunk k: piece-relative
-// position 16 k + dk0 (vcopy_kernel's).
-struct Dest {
-    uint64_t D;
-    uint32_t n, sh;
-    int dk0;
-};
-__device__ __forceinline__ Dest dest_of(uint64_t a0, uint32_t head, uint32_t rec_off, uint64_t D, uint32_t n) {
-    Dest d;
-    d.D = D;
-    d.n = n;
-    d.sh = (uint32_t)((a0 + rec_off - D) & 15u);
-    d.dk0 = (int)d.sh - (int)head - (int)rec_off;
-    return d;
-}
-
-// One step's loads (vcopy_kernel's): chunks [i0, i0 + 64 U), and for lane 63 the chunk after them.
-__device__ __forceinline__ void load_step(uint64_t base, uint32_t nch, uint32_t i0, bool next, int lane, uint64_t dummy,
-                                          u32x4 (&c)[U], u32x4& xh) {
-    const uint32_t kx = i0 + STEP;
-    xh = ld16<false>((gcv4)(next && lane == 63 && kx < nch ? base + 16ull * kx : dummy));
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint32_t k = i0 + (uint32_t)(u * 64 + lane);
-        c[u] = ld16<false>((gcv4)(k < nch ? base + 16ull * k : dummy));
-    }
-}
-
-// Each chunk's successor (the wave's lanes together: the exchange needs all of them).
-__device__ __forceinline__ void successors(const u32x4 (&c)[U], const u32x4& xh, int lane, u32x4 (&hi)[U]) {
-    u32x4 ncur = vcopy::next4<64>(c[0], lane);
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const u32x4 nnext = u + 1 < U ? vcopy::next4<64>(c[u + 1 < U ? u + 1 : u], lane) : xh;
-        hi[u] = lane == 63 ? nnext : ncur;
-        ncur = nnext;
-    }
-}
-
-// One step's stores: chunks entirely inside the range as one dwordx4 store, its first and last chunk
-// byte-masked (store_edge).
-__device__ __forceinline__ void store_piece(const Dest& d, const u32x4 (&c)[U], const u32x4 (&hi)[U], uint32_t i0, uint32_t nch,
-                                            int lane) {
-#pragma unroll
-    for (int u = 0; u < U; ++u) {
-        const uint32_t k = i0 + (uint32_t)(u * 64 + lane);
-        const int pos = (int)(16u * k) + d.dk0;
-        const int lo = -pos, end = (int)d.n - pos;
-        if (k < nch && end > 0 && lo < 16) {
-            const u32x4 m = funnel16(c[u], hi[u], d.sh);
-            const gu8 dst = (gu8)(d.D + (uint64_t)(int64_t)pos);
-            if (lo <= 0 && end >= 16) *(GMEM u32x4*)dst = m;
-            else vcopy::store_edge(dst, m, lo, end);
-        }
-    }
-}
 
 template <bool IMPLICIT>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void udprx_kernel(
@@ -137,8 +76,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void u
     const int lane = (int)(tid & 63u);
     const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(tid >> 6));
     const uint64_t dummy = (uint64_t)p.dummy;
-    u32x4* wn = &win[wave][0];
-    const uint8_t* winb = reinterpret_cast<const uint8_t*>(wn);
 
     for (uint64_t gi = blockIdx.x; gi < ngroups; gi += gridDim.x) {
         const uint64_t first = groups[gi].first;
@@ -219,54 +156,24 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void u
         // ---- 1. one pass over the wave's records: the status byte, and the speculative delivery ----
         for (uint32_t j = wave; j < count; j += 4) {
             const uint64_t r = first + j;
-            const RecRef rr = rec_at<IMPLICIT, false>(p, r);
-            const uint64_t base = rr.a0 & ~15ull;
-            const uint32_t head = (uint32_t)(rr.a0 - base);
-            const uint32_t nch = n_chunks<false>(rr);
+            const Record rec(rec_at<IMPLICIT, false>(p, r), &win[wave][0], geo[wave]);
+            const uint32_t nch = rec.nch;
             const uint32_t size = s_size[j], spec = s_spec[j];
             const bool st = size != NONE && size > 0 && spec != NONE;  // (wave-uniform)
 
             u32x4 c[U], xh;
-            load_step(base, nch, 0u, st, lane, dummy, c, xh);
-#pragma unroll
-            for (int u = 0; u * 64 < WIN_CH; ++u) {
-                const uint32_t k = (uint32_t)(u * 64 + lane);
-                if (k < (uint32_t)WIN_CH && k < nch) wn[k] = c[u];
-            }
-            wave_lds_sync();
-            // record byte o: the LDS window, else global memory (behind a long Hop-by-Hop header)
-            auto rd = [&](uint32_t o) -> uint32_t {
-                const uint32_t x = head + o;
-                if (x < (uint32_t)WIN) return (uint32_t)winb[x];
-                return ld_byte_sync(rr.a0 + o);
-            };
-            {
-                const Geom g0 = parse_geometry<false>(rd, rr.len, rr.kind, false);
-                if (lane == 0) geo[wave] = g0;
-            }
-            wave_lds_sync();
-            const Geom& g = geo[wave];
-            const bool l4 = g.proto != P_NONE && !(g.st & SMOL_ST_MALFORMED);
-            const int s1 = l4 ? (int)g.span_end : 0;
-            const Dest q = dest_of(rr.a0, head, st ? s_offp[j] & 0xffffu : 0u, ring + (st ? spec : 0u), st ? size : 0u);
+            load_step<64, U>(rec.base, nch, 0u, st, lane, dummy, c, xh);
+            const int s1 = rec.parse<64, U>(c, lane);
+            const Dest q = dest_of(rec.rr.a0, rec.head, st ? s_offp[j] & 0xffffu : 0u, ring + (st ? spec : 0u), st ? size : 0u);
 
             uint32_t acc = 0;
             for (uint32_t i0 = 0; i0 < nch; i0 += STEP) {
-                if (i0) load_step(base, nch, i0, st, lane, dummy, c, xh);
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    const uint32_t k = i0 + (uint32_t)(u * 64 + lane);
-                    if (k < nch) acc = sum_chunk(c[u], (int)(16u * k) - (int)head, s1, acc);
-                }
-                if (st) {
-                    u32x4 hi[U];
-                    successors(c, xh, lane, hi);
-                    store_piece(q, c, hi, i0, nch, lane);
-                }
+                if (i0) load_step<64, U>(rec.base, nch, i0, st, lane, dummy, c, xh);
+                acc = sum_step<64, U>(c, i0, rec, s1, lane, acc);
+                if (st) store_step<64, U>(c, xh, i0, nch, lane, q);
             }
 
-            finish_gates<64, MODE_VERIFY, false, decltype(rd)>(p, g, acc, rd, winb, head, rr.a0, r, lane, nullptr, ~0ull, ~0ull,
-                                                               0, nullptr, &s_stat[j]);
+            finish<64>(p, rec, acc, r, lane, &s_stat[j]);
             wave_lds_sync();  // the window is rewritten by the wave's next record
         }
         lds_sync();  // (all threads, whatever the group streamed) every record's verdict
@@ -321,16 +228,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(7))) void u
             __syncthreads();                                    // ... in every wave, before the second ones issue
             for (uint32_t j = wave; j < count; j += 4) {
                 if (!(s_fl[j] & SMOL_URX_RESTORED)) continue;
-                const RecRef rr = rec_at<IMPLICIT, false>(p, first + j);
-                const uint64_t base = rr.a0 & ~15ull;
-                const uint32_t head = (uint32_t)(rr.a0 - base);
-                const uint32_t nch = n_chunks<false>(rr);
-                const Dest q = dest_of(rr.a0, head, s_offp[j] & 0xffffu, ring + s_ring[j], s_size[j]);
-                for (uint32_t i0 = 0; i0 < nch; i0 += STEP) {
-                    u32x4 c[U], xh, hi[U];
-                    load_step(base, nch, i0, true, lane, dummy, c, xh);
-                    successors(c, xh, lane, hi);
-                    store_piece(q, c, hi, i0, nch, lane);
+                const Record rec(rec_at<IMPLICIT, false>(p, first + j), &win[wave][0], geo[wave]);  // (its grid only)
+                const Dest q = dest_of(rec.rr.a0, rec.head, s_offp[j] & 0xffffu, ring + s_ring[j], s_size[j]);
+                for (uint32_t i0 = 0; i0 < rec.nch; i0 += STEP) {
+                    u32x4 c[U], xh;
+                    load_step<64, U>(rec.base, rec.nch, i0, true, lane, dummy, c, xh);
+                    store_step<64, U>(c, xh, i0, rec.nch, lane, q);
                 }
             }
         }
