@@ -45,6 +45,9 @@
  *       - smol_csum_batch_verify_udp_enqueue == verify over the frames of UDP sockets, and in the same
  *         pass each datagram's payload put where the socket's PacketBuffer::enqueue places it, metadata
  *         entries written (UdpSocket::process' rx_buffer.enqueue and copy_from_slice);
+ *       - smol_csum_batch_udp_dequeue_emit == emit over the frames of UDP sockets' queued datagrams, the
+ *         frames themselves built in the same pass: the transmit PacketBuffer dequeued, the headers
+ *         written, the payload copied once (UdpSocket::dispatch's tx_buffer.dequeue_with and emit);
  *       - smol_csum_batch_data  == checksum::data() over each raw span.
  *     A device that offloads checksums (phy::Device with ChecksumCapabilities::ignored(),
  *     src/phy/mod.rs:223-233) runs emit in TxToken::consume and verify before yielding an
@@ -1202,6 +1205,147 @@ int smol_csum_batch_verify_udp_enqueue(smol_csum_ctx_t* ctx, const uint8_t* d_bu
                                        smol_csum_udprx_t* d_rx,            /* one per RECORD */
                                        smol_csum_udpsockout_t* d_out,      /* one per GROUP  */
                                        void* stream);
+
+/* ---- udp_dequeue_emit: sockets' transmit buffers drained into frames --------------------- */
+
+/* One UDP socket's transmit buffer before the call and where its frames go (96 bytes, 16-byte-aligned device
+ * array, input; one per GROUP). */
+typedef struct {
+    uint64_t src_offset;   /* byte offset of the payload ring's storage in d_src (any alignment)   */
+    uint64_t meta_first;   /* index of the metadata ring's first entry in d_meta                   */
+    uint64_t dst_offset;   /* byte offset of the group's first frame in d_dst (any alignment)      */
+    uint64_t tx_first;     /* index of the group's first entry in d_tx                             */
+    uint32_t payload_cap;  /* as smol_csum_udpsock_t: payload_ring.capacity()                      */
+    uint32_t payload_read; /* payload_ring.read_at                                                 */
+    uint32_t payload_len;  /* payload_ring.len()                                                   */
+    uint32_t meta_cap;     /* metadata_ring.capacity()                                             */
+    uint32_t meta_read;    /* metadata_ring.read_at                                                */
+    uint32_t meta_len;     /* metadata_ring.len()                                                  */
+    uint32_t dst_cap;      /* bytes available at dst_offset                                        */
+    uint32_t max_dgrams;   /* 1 .. SMOL_MAX_SOCKET_DGRAMS: PACKET entries this call may dequeue    */
+    uint16_t port;         /* endpoint.port: the source port                                       */
+    uint16_t ip_mtu;       /* DeviceCapabilities::ip_mtu()                                         */
+    uint8_t hop_limit;     /* hop_limit.unwrap_or(64), resolved by the caller                      */
+    uint8_t flags;         /* SMOL_UTXS_*; other bits must be 0                                    */
+    uint8_t eth_dst[6];    /* with SMOL_UTXS_ETH: the next hop's hardware address                  */
+    uint8_t eth_src[6];    /* with SMOL_UTXS_ETH: the interface's                                  */
+    uint8_t reserved[14];  /* must be 0                                                            */
+} smol_csum_udptxsock_t;
+#define SMOL_UTXS_ETH 0x01u /* frames carry an Ethernet header */
+
+/* One dequeued datagram (16 bytes, 16-byte-aligned device array, output): entry tx_first + k is for the k-th
+ * PACKET entry the group dequeued. */
+typedef struct {
+    uint32_t frame_off; /* of its frame, relative to dst_offset (OVERSIZE: where the next frame starts)  */
+    uint32_t ring_off;  /* payload-ring index of the first payload byte                                  */
+    uint32_t meta_idx;  /* metadata-ring index of its entry                                              */
+    uint16_t ip_len;    /* the IP packet's length: the frame is io + ip_len bytes (0 with OVERSIZE)      */
+    uint8_t flags;      /* SMOL_UTX_*                                                                    */
+    uint8_t reserved;   /* 0 */
+} smol_csum_udptx_t;
+#define SMOL_UTX_SENT     0x01u /* its frame is written                                          */
+#define SMOL_UTX_OVERSIZE 0x02u /* ip_len > ip_mtu: dequeued, no frame written                   */
+#define SMOL_UTX_PADDED   0x04u /* a PADDING entry was dequeued in front of it                   */
+
+/* One socket's outcome (32 bytes, 16-byte-aligned device array, output; one per GROUP). */
+typedef struct {
+    uint32_t payload_read; /* the ring state after the call: what the caller copies into its PacketBuffer */
+    uint32_t payload_len;
+    uint32_t meta_read;
+    uint32_t meta_len;
+    uint32_t sent;         /* entries with SMOL_UTX_SENT     */
+    uint32_t oversize;     /* entries with SMOL_UTX_OVERSIZE */
+    uint32_t bytes;        /* where the next frame would have started, relative to dst_offset (at most 2^32 - 1) */
+    uint8_t stop;          /* SMOL_UTX_STOP_*: why the group stopped dequeueing */
+    uint8_t valid;         /* 1: the socket entry was usable */
+    uint8_t reserved[2];   /* 0 */
+} smol_csum_udptxout_t;
+#define SMOL_UTX_STOP_EMPTY   1u /* the metadata ring ran empty                                        */
+#define SMOL_UTX_STOP_MAX     2u /* max_dgrams PACKET entries were dequeued                            */
+#define SMOL_UTX_STOP_NOSPACE 3u /* the next frame does not fit; its datagram stays queued             */
+#define SMOL_UTX_STOP_CORRUPT 4u /* the front entry is not a PACKET entry the payload ring can hold    */
+
+/* The send-side mirror of smol_csum_batch_verify_udp_enqueue: every socket's transmit PacketBuffer dequeued in
+ * order and each datagram written out as a whole frame, Ethernet (optional), IPv4 or IPv6 and UDP headers
+ * built on the device, both checksums filled, in one pass over the payload bytes.  In the reference a UDP send
+ * is UdpSocket::dispatch (src/socket/udp.rs:535-592): tx_buffer.dequeue_with skips a padding entry and hands
+ * out one contiguous payload (src/storage/packet_buffer.rs:169-204; src/storage/ring_buffer.rs:145-161,
+ * 239-268), dispatch_ip writes the Ethernet and IP headers (src/iface/interface/mod.rs:1245-1268, 1359-1395;
+ * src/wire/ipv4.rs:584-611, src/wire/ipv6.rs:628-640), UdpRepr::emit copies the payload and fill_checksum sums
+ * it again (src/wire/udp.rs:286-309, 194-208): two passes over every payload byte behind a serial walk of the
+ * metadata ring.  There is no smol_csum_batch_t: the input is the sockets' buffers.  A group is one socket.
+ *
+ * Metadata entries.  smol_csum_udpmeta_t is read with its send-side meaning: size is the payload bytes,
+ * src_port is endpoint.port, the DESTINATION port, remote_addr the destination address, local_addr the source
+ * address, which the caller has resolved (udp.rs:543-560); family is 4 or 6, and for IPv4 only the first 4
+ * address bytes are read; record and reserved are not read.  This is exactly the entry
+ * smol_csum_batch_verify_udp_enqueue writes for a received datagram, so a receive ring handed to this call
+ * unchanged is answered datagram by datagram, each reply going back to its sender from the address it was sent
+ * to.  Metadata index i of a group is d_meta[meta_first + i].
+ *
+ * The dequeue rule.  State (pr, pl, mr, ml) over the capacities P and M as for the enqueue rule.  One step is
+ * one dispatch call:
+ *   1. dequeue_padding (packet_buffer.rs:156-167).  When ml > 0 and the entry at mr is PADDING:
+ *      n = min(size, pl, P - pr), the clamp of dequeue_many; pr = (pr + n) % P, or 0 when P == 0; pl -= n;
+ *      mr = (mr + 1) % M; ml -= 1.  This happens whatever follows.
+ *   2. ml == 0: stop EMPTY.
+ *   3. The entry at mr must be PACKET with family 4 or 6 and size <= min(pl, P - pr) (the reference's unwrap and
+ *      debug_assert).  Otherwise stop CORRUPT; nothing more is dequeued.
+ *   4. ihl = 20 or 40; ip_len = ihl + 8 + size; io = 14 with SMOL_UTXS_ETH, else 0.
+ *   5. ip_len > ip_mtu: OVERSIZE.  The datagram IS dequeued, as dispatch_ip returning Ok does for the IPv4
+ *      fragmentation branch and for the IPv6 drop alike (mod.rs:1276-1358, 1378-1382).  Its entry carries
+ *      ring_off and meta_idx, no frame is written and the place of the next frame does not advance.  The
+ *      caller feeds an IPv4 one to smol_csum_batch_fragment_emit before it reuses the ring space.
+ *   6. Otherwise the frame is placed: with frame_stride S != 0 at frame_off = S * (frames SENT so far), with
+ *      frame_stride == 0 at the sum of the earlier frames' lengths (back to back, any alignment).  It does not
+ *      fit when frame_off + io + ip_len > dst_cap, or S != 0 and io + ip_len > S: stop NOSPACE, and the datagram
+ *      stays queued (device.transmit returning None, mod.rs:724-727; dequeue_with's Err arm,
+ *      packet_buffer.rs:199).  A padding entry step 1 dequeued in front of it is gone.
+ *   7. It is dequeued: ring_off = pr; pr = (pr + size) % P; pl -= size; mr = (mr + 1) % M; ml -= 1.
+ * Steps repeat until a stop, or until max_dgrams PACKET entries have been dequeued (SENT or OVERSIZE): stop
+ * MAX.  No further step starts then, so a padding entry behind the last one stays queued.
+ *
+ * An invalid group: reserved bytes not 0, unknown flag bits, max_dgrams 0 or above SMOL_MAX_SOCKET_DGRAMS, or
+ * a ring state outside smol_csum_udpsock_t's contract (payload_len > payload_cap, meta_len > meta_cap, a read
+ * index not below its capacity, with capacity 0 not 0).  Nothing is read from its rings, no frame or d_tx entry
+ * is written, and its d_out entry is all zero.
+ *
+ * The frame, byte for byte what smol_csum_batch_emit leaves in the same frame built on the host, under caps:
+ *   - Ethernet, with SMOL_UTXS_ETH: eth_dst, eth_src, ethertype 0x0800 / 0x86DD.
+ *   - IPv4 (Ipv4Repr::emit): 45 00, total length ip_len, ident 0, 40 00 (DF), hop_limit, protocol 17, the header
+ *     checksum under caps.ipv4.tx() else 0, source local_addr[0..4], destination remote_addr[0..4].
+ *   - IPv6: 60 00 00 00, payload length 8 + size, next header 17, hop_limit, source local_addr, destination
+ *     remote_addr.
+ *   - UDP: source port `port`, destination port the entry's src_port, length 8 + size, and the checksum, which
+ *     under caps.udp.tx() covers the pseudo-header, the header and the payload with a computed 0 written as
+ *     0xffff, else 0.
+ *   - The payload: d_src[src_offset + ring_off ..][.. size].
+ *
+ * Reads and writes.  Each payload byte is read once and each frame byte written once.  d_src is read only in
+ * 16-byte chunks that hold at least one byte of a SENT payload; d_meta and d_socks are only read.  No byte of
+ * d_dst is read, and none outside the SENT frames is written: edges go out as byte-masked stores, never
+ * read-modify-write.  d_tx entries past sent + oversize are not written.  Frame areas of different groups
+ * must not overlap.
+ *
+ * What stays with the caller: source-address selection; the neighbour lookup (one next hop per socket entry:
+ * a socket that talks to several neighbours is drained without SMOL_UTXS_ETH into strided frames and the
+ * caller writes the Ethernet headers); IPv4 fragmentation of OVERSIZE datagrams; the commit of the four state
+ * words of d_out into the PacketBuffer, and the waker.
+ *
+ * Resources.  No context scratch, no event, no allocation; stream-ordered on `stream`, graph-capturable, and
+ * calls on different streams are independent (also on one context).
+ *
+ * SMOL_EINVAL: NULL ctx, bad caps, NULL d_src / d_socks / d_meta / d_dst / d_tx / d_out with n_groups > 0,
+ * d_socks, d_meta, d_tx or d_out not 16-byte aligned.  n_groups == 0 returns SMOL_OK and launches nothing.
+ *
+ * Added within ABI 6 (SMOLCSUM_ABI_VERSION unchanged: the change is additive). */
+int smol_csum_batch_udp_dequeue_emit(smol_csum_ctx_t* ctx, const uint8_t* d_src,
+                                     const smol_csum_udptxsock_t* d_socks, uint64_t n_groups, /* one per GROUP */
+                                     const smol_csum_udpmeta_t* d_meta,  /* the metadata rings, only read */
+                                     const smol_checksum_caps_t* caps, uint8_t* d_dst, uint32_t frame_stride,
+                                     smol_csum_udptx_t* d_tx,            /* one per dequeued datagram */
+                                     smol_csum_udptxout_t* d_out,        /* one per GROUP */
+                                     void* stream);
 
 /* ---- 4. 6LoWPAN next-header-compressed UDP (RFC 6282 §4.3) ------------------------------- */
 

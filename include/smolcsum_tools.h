@@ -207,6 +207,7 @@ const char* smol_csum_tool_kernel_name(const smol_csum_ctx_t* ctx, int op, int h
  * 15 = echo_kernel (smol_csum_batch_verify_echo_reply: variant 0, G and U its launch shape);
  * 16 = unreach_kernel (smol_csum_batch_verify_unreach_reply: the same);
  * 17 = udprx_kernel (smol_csum_batch_verify_udp_enqueue: variant 0, G 64, U its chunks per lane and step);
+ * 18 = udptx_kernel (smol_csum_batch_udp_dequeue_emit: the same);
  * 0 before the first launch.  The fragment kernels of emit_frag /
  * verify_frag record nothing. */
 uint32_t smol_csum_tool_last_launch(void);

@@ -35,7 +35,8 @@ ABI_SYMBOLS = [
     "smol_csum_apply_fields", "smol_csum_batch_emit_frag",
     "smol_csum_batch_verify_frag", "smol_csum_batch_verify_reassemble", "smol_csum_batch_fragment_emit",
     "smol_csum_batch_tcp_segment_emit", "smol_csum_batch_verify_tcp_assemble", "smol_csum_batch_verify_echo_reply",
-    "smol_csum_batch_verify_unreach_reply", "smol_csum_batch_verify_udp_enqueue", "smol_csum_batch_nhc_udp_emit",
+    "smol_csum_batch_verify_unreach_reply", "smol_csum_batch_verify_udp_enqueue", "smol_csum_batch_udp_dequeue_emit",
+    "smol_csum_batch_nhc_udp_emit",
     "smol_csum_batch_nhc_udp_verify", "smol_csum_last_error", "smol_csum_abi_version",
 ]
 TOOL_SYMBOLS = [
@@ -323,6 +324,63 @@ class UdpSockOutC(ctypes.Structure):
     ]
 
 
+class UdpTxSockC(ctypes.Structure):
+    """smol_csum_udptxsock_t: one UDP socket's transmit buffer before the call and where its frames go
+    (smol_csum_batch_udp_dequeue_emit)."""
+
+    _fields_ = [
+        ("src_offset", ctypes.c_uint64),
+        ("meta_first", ctypes.c_uint64),
+        ("dst_offset", ctypes.c_uint64),
+        ("tx_first", ctypes.c_uint64),
+        ("payload_cap", ctypes.c_uint32),
+        ("payload_read", ctypes.c_uint32),
+        ("payload_len", ctypes.c_uint32),
+        ("meta_cap", ctypes.c_uint32),
+        ("meta_read", ctypes.c_uint32),
+        ("meta_len", ctypes.c_uint32),
+        ("dst_cap", ctypes.c_uint32),
+        ("max_dgrams", ctypes.c_uint32),
+        ("port", ctypes.c_uint16),
+        ("ip_mtu", ctypes.c_uint16),
+        ("hop_limit", ctypes.c_uint8),
+        ("flags", ctypes.c_uint8),
+        ("eth_dst", ctypes.c_uint8 * 6),
+        ("eth_src", ctypes.c_uint8 * 6),
+        ("reserved", ctypes.c_uint8 * 14),
+    ]
+
+
+class UdpTxC(ctypes.Structure):
+    """smol_csum_udptx_t: one dequeued datagram (smol_csum_batch_udp_dequeue_emit)."""
+
+    _fields_ = [
+        ("frame_off", ctypes.c_uint32),
+        ("ring_off", ctypes.c_uint32),
+        ("meta_idx", ctypes.c_uint32),
+        ("ip_len", ctypes.c_uint16),
+        ("flags", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8),
+    ]
+
+
+class UdpTxOutC(ctypes.Structure):
+    """smol_csum_udptxout_t: one socket's outcome (smol_csum_batch_udp_dequeue_emit)."""
+
+    _fields_ = [
+        ("payload_read", ctypes.c_uint32),
+        ("payload_len", ctypes.c_uint32),
+        ("meta_read", ctypes.c_uint32),
+        ("meta_len", ctypes.c_uint32),
+        ("sent", ctypes.c_uint32),
+        ("oversize", ctypes.c_uint32),
+        ("bytes", ctypes.c_uint32),
+        ("stop", ctypes.c_uint8),
+        ("valid", ctypes.c_uint8),
+        ("reserved", ctypes.c_uint8 * 2),
+    ]
+
+
 _LIBS = {}
 
 
@@ -405,6 +463,9 @@ def lib(path: str | None = None) -> ctypes.CDLL:
         L.smol_csum_batch_verify_udp_enqueue.argtypes = [vp, vp, ctypes.POINTER(BatchC), vp, u64, ctypes.POINTER(Caps),
                                                          vp, vp, vp, vp, vp, vp, vp]
         L.smol_csum_batch_verify_udp_enqueue.restype = i32
+    if hasattr(L, "smol_csum_batch_udp_dequeue_emit"):
+        L.smol_csum_batch_udp_dequeue_emit.argtypes = [vp, vp, vp, u64, vp, ctypes.POINTER(Caps), vp, u32, vp, vp, vp]
+        L.smol_csum_batch_udp_dequeue_emit.restype = i32
     L.smol_csum_last_error.argtypes = []
     L.smol_csum_last_error.restype = ctypes.c_char_p
     L.smol_csum_abi_version.argtypes = []

@@ -552,6 +552,24 @@ int smol_csum_batch_verify_udp_enqueue(smol_csum_ctx_t* ctx, const uint8_t* d_bu
                      [&] { return launch_udprx(p, d_groups, n_groups, v, ctx->max_blocks, (hipStream_t)stream); });
 }
 
+// Every socket's transmit PacketBuffer dequeued and its datagrams written out as frames, headers built on the
+// device, checksums filled in the pass that copies the payload (include/smolcsum.h).  No batch: the sockets'
+// buffers are the input.  Uses none of the context's scratch or events, so calls on different streams are
+// independent.
+int smol_csum_batch_udp_dequeue_emit(smol_csum_ctx_t* ctx, const uint8_t* d_src, const smol_csum_udptxsock_t* d_socks,
+                                     uint64_t n_groups, const smol_csum_udpmeta_t* d_meta, const smol_checksum_caps_t* caps,
+                                     uint8_t* d_dst, uint32_t frame_stride, smol_csum_udptx_t* d_tx,
+                                     smol_csum_udptxout_t* d_out, void* stream) {
+    if (!ctx || !caps_valid(caps)) return SMOL_EINVAL;
+    if (n_groups == 0) return SMOL_OK;
+    if (!d_src || !d_socks || !d_meta || !d_dst || !d_tx || !d_out || ((uintptr_t)d_socks & 15u) != 0 ||
+        ((uintptr_t)d_meta & 15u) != 0 || ((uintptr_t)d_tx & 15u) != 0 || ((uintptr_t)d_out & 15u) != 0)
+        return SMOL_EINVAL;
+    const UdpTxArgs v = {d_src, d_socks, d_meta, d_dst, d_tx, d_out, ctx->dummy, frame_stride, caps->ipv4, caps->udp};
+    return on_device(ctx, "udp_dequeue_emit kernel launch",
+                     [&] { return launch_udptx(v, n_groups, ctx->max_blocks, (hipStream_t)stream); });
+}
+
 // ---- 6LoWPAN NHC UDP --------------------------------------------------------------------------
 
 int smol_csum_batch_nhc_udp_emit(smol_csum_ctx_t* ctx, uint8_t* d_buf, const smol_csum_batch_t* b,

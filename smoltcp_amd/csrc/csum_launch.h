@@ -260,11 +260,12 @@ __device__ inline uint64_t logical_block(uint32_t xcd_remap) {
 // KERN_ECHO: smol_csum_batch_verify_echo_reply's kernel (no registry row; variant 0, G and U its launch shape).
 // KERN_UNREACH: smol_csum_batch_verify_unreach_reply's kernel (the same).
 // KERN_UDPRX: smol_csum_batch_verify_udp_enqueue's kernel (no registry row; variant 0, G 64, U its chunks per lane).
+// KERN_UDPTX: smol_csum_batch_udp_dequeue_emit's kernel (the same).
 enum {
     KERN_WALK = 1, KERN_TILE = 2, KERN_COPY = 3, KERN_WALK_NHC = 4, KERN_XWALK = 5, KERN_DWALK = 6,
     KERN_WALK_FIELDS = 7, KERN_XWALK_FIELDS = 8, KERN_DWALK_FIELDS = 9, KERN_VCOPY = 10,
     KERN_FRAGCOPY = 11, KERN_FRAGCUT = 12, KERN_TCPCUT = 13, KERN_TCPASM = 14, KERN_ECHO = 15,
-    KERN_UNREACH = 16, KERN_UDPRX = 17
+    KERN_UNREACH = 16, KERN_UDPRX = 17, KERN_UDPTX = 18
 };
 inline std::atomic<uint32_t> g_last_launch{0};
 inline void note_launch(uint32_t kern, uint32_t var, uint32_t g, uint32_t u) {
@@ -431,6 +432,22 @@ struct UdpRxArgs {
 };
 hipError_t launch_udprx(const KParams& p, const smol_csum_frag_group_t* groups, uint64_t ngroups,
                         const UdpRxArgs& v, uint32_t max_blocks, hipStream_t s);
+// udp_dequeue_emit (smol_csum_batch_udp_dequeue_emit, csum_udptx.hip): every socket's transmit PacketBuffer
+// dequeued (csum_pktbuf.h) and each datagram written out as a frame, headers built on the device, checksums
+// filled in the pass that copies the payload; one workgroup per socket.  No batch, so no KParams: the caps and
+// the dummy line travel here.  Outside the variant registry.
+struct UdpTxArgs {
+    const uint8_t* src;                  // the payload rings
+    const smol_csum_udptxsock_t* socks;  // one 96-B entry per group (input)
+    const smol_csum_udpmeta_t* meta;     // the metadata rings: 48-B entries (input)
+    uint8_t* dst;
+    smol_csum_udptx_t* tx;               // one 16-B entry per dequeued datagram (output)
+    smol_csum_udptxout_t* out;           // one 32-B entry per group (output)
+    const uint8_t* dummy;                // KParams::dummy
+    uint32_t frame_stride;               // 0: frames back to back
+    uint32_t caps_ipv4, caps_udp;
+};
+hipError_t launch_udptx(const UdpTxArgs& v, uint64_t ngroups, uint32_t max_blocks, hipStream_t s);
 hipError_t launch_stream_read(const uint8_t* buf, uint64_t bytes, uint32_t* sink, uint32_t max_blocks,
                               hipStream_t s);
 hipError_t launch_field_probe(uint8_t* buf, uint64_t bytes, uint64_t stride, uint32_t f1, uint32_t f2,

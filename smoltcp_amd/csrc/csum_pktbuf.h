@@ -83,4 +83,86 @@ SMOL_PKTBUF_FN bool pktbuf_state_valid(uint32_t P, uint32_t M, const PktBufState
     return s.pl <= P && s.ml <= M && (P ? s.pr < P : s.pr == 0) && (M ? s.mr < M : s.mr == 0);
 }
 
+// The dequeue rule of smol_csum_batch_udp_dequeue_emit (include/smolcsum.h): which datagram a UDP socket's
+// PacketBuffer hands out next, the text udptx_kernel (csum_udptx.hip) runs and tests/cpp/pktbuf_dequeue_asan.cpp
+// walks.
+//
+// PacketBuffer::dequeue_with (src/storage/packet_buffer.rs:169-204) over the same two RingBuffers
+// (src/storage/ring_buffer.rs:145-161 dequeue_one_with, :239-268 dequeue_many_with), statement for statement,
+// in two halves, because the closure between them (UdpSocket::dispatch's emit, src/socket/udp.rs:535-592) may
+// fail and then the packet stays queued (packet_buffer.rs:199):
+//   pktbuf_front   1. dequeue_padding (:156-167): when ml > 0 and the entry at mr is PADDING,
+//                     n = min(size, pl, P - pr) (dequeue_many's clamp); pr = (pr + n) % P, or 0 when P == 0;
+//                     pl -= n; mr = (mr + 1) % M; ml -= 1.  This happens whatever follows.
+//                  2. ml == 0: Empty (:176, dequeue_one_with's Err).
+//                  3. the entry at mr must be PACKET, of family 4 or 6, with size <= min(pl, P - pr): the
+//                     `unwrap` of :185 and the debug_assert of :191.  Otherwise Corrupt, nothing more changes.
+//                     Else the datagram is payload-ring bytes [pr, pr + size), its entry is at mr.
+//   pktbuf_take    4. the closure returned Ok: pr = (pr + size) % P; pl -= size; mr = (mr + 1) % M; ml -= 1.
+// pktbuf_dequeue is both: PacketBuffer::dequeue (:207-209).  Under the group contract pr + size <= P and
+// mr + 1 <= M, so each modulo is pktbuf_wrap's conditional subtraction here too.
+constexpr uint32_t PKTBUF_KIND_PACKET = 1u, PKTBUF_KIND_PADDING = 2u;  // SMOL_UMETA_*
+// What the rule reads of a metadata entry.
+struct PktBufEntry {
+    uint32_t size, kind, family;
+};
+// What one dequeue found.  res: PKTBUF_OK, PKTBUF_EMPTY or PKTBUF_CORRUPT, each with or without PKTBUF_PADDED
+// (a PADDING entry was dequeued in front).
+constexpr uint32_t PKTBUF_EMPTY = 8u, PKTBUF_CORRUPT = 16u;
+struct PktBufFront {
+    uint32_t res;
+    uint32_t ring_off;  // OK: payload-ring index of the datagram's first byte
+    uint32_t meta_idx;  // OK: metadata-ring index of its PACKET entry
+    uint32_t size;      // OK: its payload bytes
+    uint32_t family;    // OK: 4 or 6
+};
+
+// AT: PktBufEntry at(uint32_t metadata-ring index).
+template <class AT>
+SMOL_PKTBUF_FN PktBufFront pktbuf_front(uint32_t P, uint32_t M, PktBufState& s, const AT& at) {
+    PktBufFront r = {0u, 0u, 0u, 0u, 0u};
+    if (s.ml > 0) {                                           // 1
+        const PktBufEntry e = at(s.mr);
+        if (e.kind == PKTBUF_KIND_PADDING) {
+            uint32_t n = e.size < s.pl ? e.size : s.pl;
+            n = n < P - s.pr ? n : P - s.pr;
+            s.pr = pktbuf_wrap(s.pr, n, P);
+            s.pl -= n;
+            s.mr = pktbuf_wrap(s.mr, 1u, M);
+            s.ml -= 1;
+            r.res |= PKTBUF_PADDED;
+        }
+    }
+    if (s.ml == 0) {                                          // 2
+        r.res |= PKTBUF_EMPTY;
+        return r;
+    }
+    const PktBufEntry e = at(s.mr);                           // 3
+    const uint32_t contig = s.pl < P - s.pr ? s.pl : P - s.pr;
+    if (e.kind != PKTBUF_KIND_PACKET || (e.family != 4u && e.family != 6u) || e.size > contig) {
+        r.res |= PKTBUF_CORRUPT;
+        return r;
+    }
+    r.res |= PKTBUF_OK;
+    r.ring_off = s.pr;
+    r.meta_idx = s.mr;
+    r.size = e.size;
+    r.family = e.family;
+    return r;
+}
+
+SMOL_PKTBUF_FN void pktbuf_take(uint32_t P, uint32_t M, PktBufState& s, uint32_t size) {  // 4
+    s.pr = pktbuf_wrap(s.pr, size, P);
+    s.pl -= size;
+    s.mr = pktbuf_wrap(s.mr, 1u, M);
+    s.ml -= 1;
+}
+
+template <class AT>
+SMOL_PKTBUF_FN PktBufFront pktbuf_dequeue(uint32_t P, uint32_t M, PktBufState& s, const AT& at) {
+    const PktBufFront r = pktbuf_front(P, M, s, at);
+    if (r.res & PKTBUF_OK) pktbuf_take(P, M, s, r.size);
+    return r;
+}
+
 }  // namespace smolcsum

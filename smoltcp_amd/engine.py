@@ -17,7 +17,8 @@ import numpy as np
 
 from . import _lib
 from ._lib import (NO_FIELD, BatchC, Caps, DgramC, EchoC, EchoCfgC, FieldsC, FragOutC, FragPlanC, SlotC, SpanC, TcpFlowC,
-                   TcpOutC, TcpPlanC, TcpSegC, TcpWinC, UdpMetaC, UdpRxC, UdpSockC, UdpSockOutC, UnreachC, check, lib)
+                   TcpOutC, TcpPlanC, TcpSegC, TcpWinC, UdpMetaC, UdpRxC, UdpSockC, UdpSockOutC, UdpTxC, UdpTxOutC, UdpTxSockC,
+                   UnreachC, check, lib)
 from .phy import ChecksumCapabilities
 
 KIND_RAW, KIND_IP, KIND_ETH = 0, 1, 2
@@ -116,6 +117,24 @@ assert UDPSOCKOUT_DTYPE.itemsize == 32 == ctypes.sizeof(UdpSockOutC)
 MAX_SOCKET_DGRAMS = 256
 URX_UDP, URX_ENQUEUED, URX_FULL, URX_PADDED, URX_RESTORED = 0x01, 0x02, 0x04, 0x08, 0x10  # SMOL_URX_*
 UMETA_PACKET, UMETA_PADDING = 1, 2  # SMOL_UMETA_*
+# smol_csum_udptxsock_t / smol_csum_udptx_t / smol_csum_udptxout_t: a UDP socket's transmit buffer before the call
+# and where its frames go, a dequeued datagram's and a socket's outcome (smol_csum_batch_udp_dequeue_emit)
+UDPTXSOCK_DTYPE = np.dtype([("src_offset", "<u8"), ("meta_first", "<u8"), ("dst_offset", "<u8"), ("tx_first", "<u8"),
+                            ("payload_cap", "<u4"), ("payload_read", "<u4"), ("payload_len", "<u4"), ("meta_cap", "<u4"),
+                            ("meta_read", "<u4"), ("meta_len", "<u4"), ("dst_cap", "<u4"), ("max_dgrams", "<u4"),
+                            ("port", "<u2"), ("ip_mtu", "<u2"), ("hop_limit", "u1"), ("flags", "u1"), ("eth_dst", "u1", (6,)),
+                            ("eth_src", "u1", (6,)), ("reserved", "u1", (14,))])
+assert UDPTXSOCK_DTYPE.itemsize == 96 == ctypes.sizeof(UdpTxSockC)
+UDPTX_DTYPE = np.dtype([("frame_off", "<u4"), ("ring_off", "<u4"), ("meta_idx", "<u4"), ("ip_len", "<u2"), ("flags", "u1"),
+                        ("reserved", "u1")])
+assert UDPTX_DTYPE.itemsize == 16 == ctypes.sizeof(UdpTxC)
+UDPTXOUT_DTYPE = np.dtype([("payload_read", "<u4"), ("payload_len", "<u4"), ("meta_read", "<u4"), ("meta_len", "<u4"),
+                           ("sent", "<u4"), ("oversize", "<u4"), ("bytes", "<u4"), ("stop", "u1"), ("valid", "u1"),
+                           ("reserved", "u1", (2,))])
+assert UDPTXOUT_DTYPE.itemsize == 32 == ctypes.sizeof(UdpTxOutC)
+UTXS_ETH = 0x01  # SMOL_UTXS_ETH
+UTX_SENT, UTX_OVERSIZE, UTX_PADDED = 0x01, 0x02, 0x04  # SMOL_UTX_*
+UTX_STOP_EMPTY, UTX_STOP_MAX, UTX_STOP_NOSPACE, UTX_STOP_CORRUPT = 1, 2, 3, 4  # SMOL_UTX_STOP_*
 
 
 def make_port_map(open_ports) -> np.ndarray:
@@ -187,6 +206,35 @@ def make_udpsocks(dst_offsets, meta_firsts, payload_caps, payload_reads, payload
                       ("meta_cap", meta_caps), ("meta_read", meta_reads), ("meta_len", meta_lens)):
         s[name] = np.broadcast_to(np.asarray(val, dtype=np.uint32), (n,))
     s["port"] = np.broadcast_to(np.asarray(ports, dtype=np.uint16), (n,))
+    return s
+
+
+def make_udptxsocks(src_offsets, meta_firsts, dst_offsets, tx_firsts, payload_caps, payload_reads, payload_lens, meta_caps,
+                    meta_reads, meta_lens, dst_caps, max_dgrams, ports, ip_mtus, hop_limits=64, eth=None) -> np.ndarray:
+    """Host array of smol_csum_udptxsock_t (view it as uint8 and copy it to the device): per socket, where its
+    payload ring's storage lies in `src`, its metadata ring's first entry in `meta`, its first frame in `dst` and
+    its first entry in `tx`; the two rings' capacity / read index / length as the PacketBuffer holds them before
+    the call; the bytes available for frames, the datagrams the call may dequeue, the source port, the IP MTU and
+    the hop limit.  `eth`: None for frames without an Ethernet header, else (eth_dst, eth_src), six bytes each (one
+    pair for all sockets, or n x 6 arrays)."""
+    n = len(src_offsets)
+    s = np.zeros(n, dtype=UDPTXSOCK_DTYPE)
+    s["src_offset"] = np.asarray(src_offsets, dtype=np.uint64)
+    for name, val in (("meta_first", meta_firsts), ("dst_offset", dst_offsets), ("tx_first", tx_firsts)):
+        s[name] = np.broadcast_to(np.asarray(val, dtype=np.uint64), (n,))
+    for name, val in (("payload_cap", payload_caps), ("payload_read", payload_reads), ("payload_len", payload_lens),
+                      ("meta_cap", meta_caps), ("meta_read", meta_reads), ("meta_len", meta_lens), ("dst_cap", dst_caps),
+                      ("max_dgrams", max_dgrams)):
+        s[name] = np.broadcast_to(np.asarray(val, dtype=np.uint32), (n,))
+    s["port"] = np.broadcast_to(np.asarray(ports, dtype=np.uint16), (n,))
+    s["ip_mtu"] = np.broadcast_to(np.asarray(ip_mtus, dtype=np.uint16), (n,))
+    s["hop_limit"] = np.broadcast_to(np.asarray(hop_limits, dtype=np.uint8), (n,))
+    if eth is not None:
+        s["flags"] = UTXS_ETH
+        s["eth_dst"] = np.broadcast_to(np.frombuffer(bytes(eth[0]), np.uint8) if isinstance(eth[0], (bytes, bytearray))
+                                       else np.asarray(eth[0], dtype=np.uint8), (n, 6))
+        s["eth_src"] = np.broadcast_to(np.frombuffer(bytes(eth[1]), np.uint8) if isinstance(eth[1], (bytes, bytearray))
+                                       else np.asarray(eth[1], dtype=np.uint8), (n, 6))
     return s
 
 
@@ -711,6 +759,39 @@ class ChecksumEngine:
               "smol_csum_batch_verify_udp_enqueue")
         return status, rx, out
 
+    def udp_dequeue_emit(self, src, socks, meta, dst, frame_stride: int = 0, caps=None, tx=None, out=None, n_tx=None,
+                         stream=None):
+        """Every socket's transmit PacketBuffer dequeued and its datagrams written to `dst` as whole frames,
+        headers built on the device, checksums filled in the pass that copies the payload
+        (smol_csum_batch_udp_dequeue_emit).  `src`: the uint8 device tensor that holds the payload rings; `socks`:
+        a device uint8 tensor of one smol_csum_udptxsock_t per socket (see make_udptxsocks); `meta`: the 16-byte
+        aligned uint8 device tensor that holds the metadata rings (48 bytes per entry, UDPMETA_DTYPE, read with
+        their send-side meaning); `frame_stride`: bytes from one frame of a socket to the next, 0 for frames
+        back to back.  Returns (tx, out): an n_tx x 16 uint8 device tensor of smol_csum_udptx_t (UDPTX_DTYPE; a
+        fresh one starts zeroed and has `n_tx` entries, which must cover every socket's tx_first + max_dgrams)
+        and an n_groups x 32 one of smol_csum_udptxout_t (UDPTXOUT_DTYPE).  Commit by copying the four state
+        words of `out` into the socket's PacketBuffer."""
+        import torch
+
+        assert socks.is_cuda and socks.is_contiguous() and (socks.numel() * socks.dtype.itemsize) % 96 == 0
+        ng = socks.numel() * socks.dtype.itemsize // 96
+        assert src.is_cuda and src.dtype.itemsize == 1 and src.is_contiguous()
+        assert dst.is_cuda and dst.dtype.itemsize == 1 and dst.is_contiguous()
+        assert meta.is_cuda and meta.is_contiguous()
+        if tx is None:
+            assert n_tx is not None, "udp_dequeue_emit: pass tx, or n_tx for a fresh one"
+            tx = torch.zeros((int(n_tx), 16), dtype=torch.uint8, device=src.device)
+        if out is None:
+            out = torch.empty((ng, 32), dtype=torch.uint8, device=src.device)
+        assert tx.is_cuda and tx.is_contiguous()
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.dtype.itemsize >= 32 * ng
+        c = _caps(caps)
+        check(self._L.smol_csum_batch_udp_dequeue_emit(self._h, src.data_ptr(), socks.data_ptr(), ng, meta.data_ptr(),
+                                                     ctypes.byref(c), dst.data_ptr(), int(frame_stride), tx.data_ptr(),
+                                                     out.data_ptr(), self._stream(stream)),
+              "smol_csum_batch_udp_dequeue_emit")
+        return tx, out
+
     # ---- tooling ----
     def synth(self, buf, batch: Batch, profile: int, seed: int, stream=None):
         self._check_buf(buf, batch)
@@ -821,14 +902,14 @@ class ChecksumEngine:
     def last_launch(self) -> dict:
         """The kernel instantiation of the process's last checksum launch: {"kernel": "csum_kernel" |
         "csum_tile_kernel" | "copy_kernel" | "csum_kernel_nhc" | "xwalk_kernel" | "dwalk_kernel" | emit_fields'
-        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel" | verify_tcp_assemble's "tcpasm_kernel" | verify_echo_reply's "echo" | verify_unreach_reply's "unreach" | verify_udp_enqueue's "udprx_kernel", "variant": VAR, "G":
+        "csum_fields_kernel" | "xwalk_kernel(fields)" | "dwalk_kernel(fields)" | verify_copy's "vcopy_kernel" | verify_reassemble's "fragcopy_kernel" | fragment_emit's "fragcut_kernel" | tcp_segment_emit's "tcpcut_kernel" | verify_tcp_assemble's "tcpasm_kernel" | verify_echo_reply's "echo" | verify_unreach_reply's "unreach" | verify_udp_enqueue's "udprx_kernel" | udp_dequeue_emit's "udptx_kernel", "variant": VAR, "G":
         lanes per record, "U": chunks per lane per step (xwalk_kernel: 1-KiB loads per record)} (None
         before the first launch)."""
         w = int(self._L.smol_csum_tool_last_launch())
         names = {1: "csum_kernel", 2: "csum_tile_kernel", 3: "copy_kernel", 4: "csum_kernel_nhc", 5: "xwalk_kernel",
                  6: "dwalk_kernel", 7: "csum_fields_kernel", 8: "xwalk_kernel(fields)", 9: "dwalk_kernel(fields)", 10: "vcopy_kernel",
                  11: "fragcopy_kernel", 12: "fragcut_kernel", 13: "tcpcut_kernel", 14: "tcpasm_kernel", 15: "echo", 16: "unreach",
-                 17: "udprx_kernel"}
+                 17: "udprx_kernel", 18: "udptx_kernel"}
         if not w >> 24:
             return None
         return {"kernel": names.get(w >> 24, "?"), "variant": (w >> 16) & 0xff, "G": (w >> 8) & 0xff, "U": w & 0xff}

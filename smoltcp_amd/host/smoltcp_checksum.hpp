@@ -367,6 +367,26 @@ public:
               "smol_csum_batch_verify_udp_enqueue");
     }
 
+    // The send-side mirror: every socket's transmit PacketBuffer dequeued in order (tx_buffer.dequeue_with,
+    // src/storage/packet_buffer.rs:169-204) and each datagram written to d_dst as a whole frame, Ethernet (with
+    // SMOL_UTXS_ETH), IP and UDP headers built on the device from d_socks[g] and the metadata entry, checksums
+    // filled under `caps`, in the pass that copies the payload: UdpSocket::dispatch (src/socket/udp.rs:535-592)
+    // for a burst.  A group is one socket; there is no batch.  d_meta entries are read with their send-side
+    // meaning (remote_addr / src_port: where to send; local_addr: what to send from), which is what
+    // verify_udp_enqueue writes, so a receive ring can be answered unchanged.  d_tx gets one entry per dequeued
+    // datagram from d_socks[g].tx_first on, d_out[g] the ring state after the call: commit by copying its four
+    // state words into the PacketBuffer.  OVERSIZE datagrams are dequeued and not written: fragment the IPv4
+    // ones with fragment_emit before reusing the ring space.  d_src, d_socks and d_meta are only read.
+    void udp_dequeue_emit(const uint8_t* d_src, const smol_csum_udptxsock_t* d_socks, uint64_t n_groups,
+                          const smol_csum_udpmeta_t* d_meta, uint8_t* d_dst, uint32_t frame_stride,
+                          smol_csum_udptx_t* d_tx, smol_csum_udptxout_t* d_out,
+                          const smoltcp::phy::ChecksumCapabilities& caps = {}, void* stream = nullptr) {
+        auto cc = caps.c();
+        check(smol_csum_batch_udp_dequeue_emit(ctx_, d_src, d_socks, n_groups, d_meta, &cc, d_dst, frame_stride, d_tx, d_out,
+                                               stream),
+              "smol_csum_batch_udp_dequeue_emit");
+    }
+
     // 6LoWPAN NHC UDP (sixlowpan::nhc::UdpNhcRepr::emit / ::parse): every record is a LOWPAN_NHC
     // UDP packet; d_addrs[i] holds record i's IPv6 addresses (IPHC-decompressed).
     void nhc_udp_emit(uint8_t* d_buf, const Batch& b, const smol_ipv6_addr_pair_t* d_addrs,
